@@ -3,6 +3,7 @@
 MI355X HIP engine (BASELINE.json metric), one process per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config amass16] [--scaling weak|strong]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 A "step" is one full sample() call: the T-step reverse chain over one batch of
@@ -14,7 +15,12 @@ fixed as N grows); --scaling strong: the `batch` sequences are split over the N 
 (sharded.shard_range), total work fixed.  Weights are the repo's deterministic synthetic filler
 (no checkpoint can be fetched); conditioning latents are synthetic U(-1, 1).
 
-Rank 0 prints one JSON line.  It also carries:
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the K steps and prints the
+headline figure (metric, value, unit, ms_per_step, dtype, the configuration and the kernels the
+timed calls ran).  --dump-outputs DIR then writes what the last timed sample() call returned as
+DIR/<name>.npy (float32; DUMP_LIMIT_BYTES at most, a fixed seeded sample of the rows beyond that):
+the inputs depend on the arguments only, so two builds can be compared output for output.
+--full adds the legs that take runs of their own; the line then also carries:
   roofline      the dominant kernel class: one graph-linear layer (on the split routes its GEMM
                 phase + mixing / attention phase; fused to_qkv + attention launches included),
                 >= 97 % of a denoise step's kernel time.  Bound "hbm": achieved = the layer's
@@ -58,6 +64,7 @@ METRIC = "generated futures/sec (AMASS 16-joint, 50 futures, T=100) at 1/2/4/8 G
 FP32_PEAK_TFLOPS = 157.3   # MI355X fp32 dense (vector = matrix), MI355X_MICROARCH.md
 F16_MFMA_PEAK_TFLOPS = 2500.0  # MI355X f16/bf16 dense MFMA (no sparsity), MI355X_MICROARCH.md
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # --dump-outputs: all files together
 
 # BASELINE.json configs -> (skeleton, T, batch sequences, futures)
 CONFIGS = {
@@ -239,6 +246,24 @@ def cpu_baseline(d, x_cond, rows, steps, threads, repeats=3):
                       f"{threads} threads (torch.set_num_threads)"}
 
 
+def dump_outputs(path, result):
+    """Write what sample() returned, (latents, start noise or None), as float32 .npy files under
+    `path`, DUMP_LIMIT_BYTES at most in all: of a larger result, the same seeded choice of rows
+    (ascending) from every array."""
+    os.makedirs(path, exist_ok=True)
+    named = [(n, t) for n, t in zip(("latents", "start_noise"), result) if torch.is_tensor(t)]
+    row_bytes = sum(t[0].numel() * 4 for _, t in named)
+    rows = named[0][1].shape[0]
+    keep = None
+    if rows * row_bytes > DUMP_LIMIT_BYTES:
+        n = DUMP_LIMIT_BYTES // row_bytes
+        keep = torch.from_numpy(np.sort(np.random.default_rng(0).choice(rows, size=n, replace=False)))
+    for name, t in named:
+        if keep is not None:
+            t = t.index_select(0, keep.to(t.device))
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def world_rows(world: int, rows: int, scaling: str, batch: int, futures: int) -> int:
     """Rows all ranks process per step: weak = world x this rank's rows; strong = the batch."""
     return batch * futures if scaling == "strong" else world * rows
@@ -256,6 +281,10 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--precision", choices=["f32", "half", "bf16"], default=None,
                     help="graph-linear arithmetic (default: the config's; f32 for the BASELINE metric)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed sample() returned as DIR/<name>.npy (rank 0's shard)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the per-kernel / roofline profile, the exact-f32 line and the CPU baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-steps", type=int, default=4)
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: every physical core this process may use")
@@ -311,7 +340,7 @@ def main():
     def step(i):
         # the metric's definition: wall time of the public NonisotropicGaussianDiffusion.sample()
         # (base.py:439-443 -> p_sample_loop -> torch.ops.skeldiff.sample_loop), output buffer reused
-        d.sample(batch_size=rows, x_cond=x_cond, seed=base_seed + i, row0=row0, out=out)
+        return d.sample(batch_size=rows, x_cond=x_cond, seed=base_seed + i, row0=row0, out=out)
 
     with torch.cuda.stream(stream):
         for i in range(args.warmup):
@@ -321,8 +350,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
+        last = None
         for i in range(args.steps):
-            step(i)
+            last = step(i)
         torch.cuda.synchronize(dev)
         if dist:
             dist.barrier()
@@ -336,9 +366,12 @@ def main():
             tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = float(tt.item())
-        ms, cnt, fl = profile_kernels(d, x_cond, rows, args.profile_reps)
+        if args.dump_outputs and rank == 0 and last is not None:  # before the --full legs reuse `out`
+            dump_outputs(args.dump_outputs, last)
+        if args.full:
+            ms, cnt, fl = profile_kernels(d, x_cond, rows, args.profile_reps)
         exact = None
-        if (world == 1 and not args.no_exact_line and args.kernel_variant == 0 and J in (16, 17, 21)
+        if (args.full and world == 1 and not args.no_exact_line and args.kernel_variant == 0 and J in (16, 17, 21)
                 and eng.precision == "f32"):
             # the same workload on the exact-f32 kernels: a second plan, same inputs
             eng.set_option("kernel_variant", 3)
@@ -369,37 +402,7 @@ def main():
              "v5 (k_gl4t + k_gl5_mixd + k_attention)" if route_bits & 32 and split else
              "one-kernel (k_gl4)" if split else "exact f32")
     half = split and eng.precision in ("half", "bf16")
-    # the to_qkv layer's mixing inside the attention launch (k_attention_mix): to_qkv + attention
-    # count as one fused layer (its bytes, FLOPs and both launches' time), as on the fused routes
-    attn_mix = bool(route_bits & 1024)
-    fused_attn = (ms[1] == 0.0 and cnt[1] == 0) or attn_mix  # attention inside the layer's launches
-    gl_ms = ms[0] + (ms[1] if attn_mix else 0.0)
-    gl_flops = fl[0] + (fl[1] if fused_attn else 0.0)
-    gl_tflops = gl_flops / (gl_ms * 1e-3) / 1e12
-    peak = F16_MFMA_PEAK_TFLOPS if half else F16_MFMA_PEAK_TFLOPS / 3.0 if split else FP32_PEAK_TFLOPS
-    gl_bytes = graph_linear_bytes(d, rows, fused_attn)
-    gl_gbs = gl_bytes / (gl_ms * 1e-3) / 1e9
-    launches = max(cnt[0], 1)
-    upd_bytes = 3.0 * rows * J * D * 4        # x0, x_t in, x_{t-1} out (device Philox noise)
-    upd_gbs = upd_bytes / (ms[2] * 1e-3) / 1e9
-    step_flops = sum(fl)
     ms_step = elapsed / args.steps * 1e3
-    # graph-linear work of the timed region: T denoise steps per bench step, on this rank's rows
-    timed_tflops = (fl[0] + fl[1]) * T / (ms_step * 1e-3) / 1e12
-    if exact is not None:
-        exact["graph_linear_tflops_timed"] = (fl[0] + fl[1]) * T / (exact["ms_per_step"] * 1e-3) / 1e12
-        exact["frac_of_f32_peak"] = exact["graph_linear_tflops_timed"] / FP32_PEAK_TFLOPS
-    traffic, traffic_note = None, "no PMC pass on record for this config and kernel set"
-    traffic_file = os.path.join(HERE, "profiles", "pmc_traffic.json")
-    traffic_key = f"{args.config}|{route_bits}"
-    if os.path.exists(traffic_file):
-        try:
-            tr = json.load(open(traffic_file)).get(traffic_key)
-            if tr and tr.get("rows") == rows:
-                traffic = tr.get("hbm_bytes_per_layer_launch")
-                traffic_note = tr.get("source")
-        except Exception:
-            pass
     rec = {
         "metric": METRIC,
         "value": value,
@@ -430,37 +433,70 @@ def main():
                    "parallelism": f"dp{world} (sequence-sharded, no data-path collective)",
                    "row_chains": row_chains, "route": route, "kernels": kernels, "route_bits": route_bits,
                    "kernel_variant": variant},
-        "roofline": {
-            "bound": "hbm",
-            "kernel": "one graph-linear layer: " + route + " (the launches of one StaticGraphLinear, to_qkv + "
-                      "attention fused); per-launch average over the layers of one denoise step",
-            "achieved": gl_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gl_gbs / HBM_PEAK_GBS,
-            "traffic": traffic, "traffic_source": traffic_note,
-            "algorithmic_bytes_per_launch": gl_bytes / launches, "avg_launch_ms": gl_ms / launches,
-            "launches_per_denoise_step": cnt[0],
-            "measured_on": ("HIP events on the launch stream around each layer, one denoise step at the full "
-                            "batch on one stream (sd_profile_step, kernels alone on the GPU), "
-                            f"{args.profile_reps} repetitions"),
-            "mfma_view": {"achieved": gl_tflops, "peak": peak, "unit": "TFLOP/s", "frac": gl_tflops / peak,
-                          "flops_per_launch": gl_flops / launches,
-                          "peak_basis": "f16 / bf16 dense MFMA 2500 TFLOP/s (one product per multiply-add)" if half
-                          else "f16 dense MFMA 2500 TFLOP/s / 3 products per f32 product" if split
-                          else "f32 dense 157.3 TFLOP/s"},
-            "timed_region": {"achieved": timed_tflops, "peak": peak, "unit": "TFLOP/s", "frac": timed_tflops / peak,
-                             "flops_per_denoise_step": fl[0] + fl[1],
-                             "measured_on": "graph-linear + attention FLOPs of T denoise steps over this rank's rows "
-                                            "/ ms_per_step (row chains, hipGraphs, update kernels, gaps inside)"},
-        },
-        "kernels_per_denoise_step_ms": {"graph_linear": ms[0], "attention": ms[1], "update": ms[2],
-                                        "step_first_to_last_event": ms[3]},
-        "update_kernel": {"bound": "hbm", "achieved": upd_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                          "frac": upd_gbs / HBM_PEAK_GBS, "bytes_per_launch": upd_bytes,
-                          "avg_launch_ms": ms[2] / max(cnt[2], 1)},
-        "step_algorithmic_tflops_per_gpu": step_flops * T * args.steps / elapsed / 1e12,
     }
+    if args.full:
+        # the to_qkv layer's mixing inside the attention launch (k_attention_mix): to_qkv + attention
+        # count as one fused layer (its bytes, FLOPs and both launches' time), as on the fused routes
+        attn_mix = bool(route_bits & 1024)
+        fused_attn = (ms[1] == 0.0 and cnt[1] == 0) or attn_mix  # attention inside the layer's launches
+        gl_ms = ms[0] + (ms[1] if attn_mix else 0.0)
+        gl_flops = fl[0] + (fl[1] if fused_attn else 0.0)
+        gl_tflops = gl_flops / (gl_ms * 1e-3) / 1e12
+        peak = F16_MFMA_PEAK_TFLOPS if half else F16_MFMA_PEAK_TFLOPS / 3.0 if split else FP32_PEAK_TFLOPS
+        gl_bytes = graph_linear_bytes(d, rows, fused_attn)
+        gl_gbs = gl_bytes / (gl_ms * 1e-3) / 1e9
+        launches = max(cnt[0], 1)
+        upd_bytes = 3.0 * rows * J * D * 4        # x0, x_t in, x_{t-1} out (device Philox noise)
+        upd_gbs = upd_bytes / (ms[2] * 1e-3) / 1e9
+        step_flops = sum(fl)
+        # graph-linear work of the timed region: T denoise steps per bench step, on this rank's rows
+        timed_tflops = (fl[0] + fl[1]) * T / (ms_step * 1e-3) / 1e12
+        if exact is not None:
+            exact["graph_linear_tflops_timed"] = (fl[0] + fl[1]) * T / (exact["ms_per_step"] * 1e-3) / 1e12
+            exact["frac_of_f32_peak"] = exact["graph_linear_tflops_timed"] / FP32_PEAK_TFLOPS
+        traffic, traffic_note = None, "no PMC pass on record for this config and kernel set"
+        traffic_file = os.path.join(HERE, "profiles", "pmc_traffic.json")
+        traffic_key = f"{args.config}|{route_bits}"
+        if os.path.exists(traffic_file):
+            try:
+                tr = json.load(open(traffic_file)).get(traffic_key)
+                if tr and tr.get("rows") == rows:
+                    traffic = tr.get("hbm_bytes_per_layer_launch")
+                    traffic_note = tr.get("source")
+            except Exception:
+                pass
+        rec.update({
+            "roofline": {
+                "bound": "hbm",
+                "kernel": "one graph-linear layer: " + route + " (the launches of one StaticGraphLinear, to_qkv + "
+                          "attention fused); per-launch average over the layers of one denoise step",
+                "achieved": gl_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gl_gbs / HBM_PEAK_GBS,
+                "traffic": traffic, "traffic_source": traffic_note,
+                "algorithmic_bytes_per_launch": gl_bytes / launches, "avg_launch_ms": gl_ms / launches,
+                "launches_per_denoise_step": cnt[0],
+                "measured_on": ("HIP events on the launch stream around each layer, one denoise step at the full "
+                                "batch on one stream (sd_profile_step, kernels alone on the GPU), "
+                                f"{args.profile_reps} repetitions"),
+                "mfma_view": {"achieved": gl_tflops, "peak": peak, "unit": "TFLOP/s", "frac": gl_tflops / peak,
+                              "flops_per_launch": gl_flops / launches,
+                              "peak_basis": "f16 / bf16 dense MFMA 2500 TFLOP/s (one product per multiply-add)" if half
+                              else "f16 dense MFMA 2500 TFLOP/s / 3 products per f32 product" if split
+                              else "f32 dense 157.3 TFLOP/s"},
+                "timed_region": {"achieved": timed_tflops, "peak": peak, "unit": "TFLOP/s", "frac": timed_tflops / peak,
+                                 "flops_per_denoise_step": fl[0] + fl[1],
+                                 "measured_on": "graph-linear + attention FLOPs of T denoise steps over this rank's rows "
+                                                "/ ms_per_step (row chains, hipGraphs, update kernels, gaps inside)"},
+            },
+            "kernels_per_denoise_step_ms": {"graph_linear": ms[0], "attention": ms[1], "update": ms[2],
+                                            "step_first_to_last_event": ms[3]},
+            "update_kernel": {"bound": "hbm", "achieved": upd_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                              "frac": upd_gbs / HBM_PEAK_GBS, "bytes_per_launch": upd_bytes,
+                              "avg_launch_ms": ms[2] / max(cnt[2], 1)},
+            "step_algorithmic_tflops_per_gpu": step_flops * T * args.steps / elapsed / 1e12,
+        })
     if exact is not None:
         rec["exact_f32"] = exact
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         threads, cores = physical_cores()
         rec["cpu_baseline"] = cpu_baseline(d, x_cond, rows, args.cpu_steps, args.cpu_threads or threads)
         rec["cpu_baseline"]["host_cores"] = cores

@@ -6,7 +6,7 @@ OUT=gpurun_out/${1:-configs}
 mkdir -p $OUT
 run() {  # name, bench args...
   local name=$1; shift
-  timeout -k 10 300 python -u bench.py "$@" --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline --no-exact-line > $OUT/$name.json 2> $OUT/$name.err
+  timeout -k 10 300 python -u bench.py --full "$@" --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline --no-exact-line > $OUT/$name.json 2> $OUT/$name.err
   local rc=$?; [ $rc -eq 0 ] || { echo "$name rc=$rc"; return $rc; }
   python3 -c "import json; r=json.load(open('$OUT/$name.json')); print('$name |', r['config']['rows_per_gpu'], 'rows | T', r['config']['T'], '|', round(r['value'],1), r['unit'], '|', r['config']['route'], '| chains', r['config']['row_chains'], '| timed frac', round(r['roofline']['timed_region']['frac'],3))"
 }

@@ -6,7 +6,7 @@
 # Environment: REPS (default 2), STEPS (default 3), ENVS (space-separated VAR=value applied to all).
 OUT=gpurun_out/ab
 mkdir -p $OUT
-B="--no-cpu-baseline --no-exact-line --profile-reps 1 --steps ${STEPS:-3} --warmup 1"
+B="--full --no-cpu-baseline --no-exact-line --profile-reps 1 --steps ${STEPS:-3} --warmup 1"
 for i in $(seq ${REPS:-2}); do
   for run in "$@"; do
     cfg=${run%%|*}; opts=${run#*|}

@@ -6,7 +6,7 @@
 TAG=${1:-close}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-timeout -k 10 600 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 600 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 rc=$?; echo "bench rc=$rc"; [ $rc -eq 0 ] || exit $rc
 bash tools/prof_bench.sh $TAG || exit $?
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
@@ -18,5 +18,5 @@ timeout -s KILL 120 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WA
     -d $OUT/pmc_kgemm/p1 -o run -- python3 tools/bench_train.py --J 16 --rows 1024 --steps 1 --warmup 1 --modes hip \
     > $OUT/pmc_kgemm/p1.log 2>&1
 rc=$?; echo "k_gemm pmc rc=$rc"; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 600 python -u bench.py --config mano51 --no-cpu-baseline --no-exact-line > $OUT/bench_mano51.json 2> $OUT/bench_mano51.err
+timeout -k 10 600 python -u bench.py --full --config mano51 --no-cpu-baseline --no-exact-line > $OUT/bench_mano51.json 2> $OUT/bench_mano51.err
 rc=$?; echo "mano51 rc=$rc"; exit $rc
