@@ -184,6 +184,15 @@ int sd_noise_fill(float* out, int64_t rows, int64_t n_per_row, uint64_t seed, in
 int sd_philox_raw(uint32_t* out, int64_t rows, int64_t quads, uint64_t seed, int64_t row0,
                   int32_t step, void* stream);
 
+/* Row-chain boundaries of sd_sample_loop (host arithmetic, no device): the first row of chain i
+ * of `nchains` over `rows` rows; i >= nchains gives `rows`.  unit <= 32: cuts on 32-row blocks,
+ * chain i starting at ceil(rows / 32) * i / nchains * 32.  A larger unit (a multiple of 32) cuts
+ * on that many rows instead where every chain then keeps at least 512 rows, and on 32 otherwise.
+ * sd_sample_loop passes sd_chain_tile_unit() -- the tiled GEMM phase's row group -- when the call
+ * takes the tiled split route on more than one chain, and 32 everywhere else. */
+int64_t sd_chain_start(int64_t rows, int32_t nchains, int64_t unit, int32_t i);
+int64_t sd_chain_tile_unit(void);
+
 /* Number of kernel launches one reverse step (denoiser + update) issues. */
 int32_t sd_plan_kernels_per_step(const sd_plan* plan);
 

@@ -40,7 +40,7 @@ EXPORTED = (
     "sd_attn_train_backward", "sd_film_tanh_forward", "sd_film_tanh_backward", "sd_l1norm_rows_forward",
     "sd_l1norm_rows_backward", "sd_rmsnorm_workspace_bytes", "sd_rmsnorm_forward", "sd_rmsnorm_backward",
     "sd_mahalanobis_loss_forward", "sd_mahalanobis_loss_backward", "sd_best_of_k", "sd_best_of_k_backward",
-    "sd_pose_loss", "sd_test_set_split_route",
+    "sd_pose_loss", "sd_test_set_split_route", "sd_chain_start", "sd_chain_tile_unit",
 )
 
 # sd_plan_set_option keys (include/skeldiff.h)
@@ -117,6 +117,8 @@ def _declare(lib: ctypes.CDLL) -> None:
         "sd_noise_fill": (ctypes.c_int, [vp, i64, i64, u64, i64, i32, vp]),
         "sd_philox_raw": (ctypes.c_int, [vp, i64, i64, u64, i64, i32, vp]),
         "sd_plan_kernels_per_step": (i32, [vp]),
+        "sd_chain_start": (i64, [i64, i32, i64, i32]),
+        "sd_chain_tile_unit": (i64, []),
         "sd_plan_step_flops": (ctypes.c_int, [vp, i64, ctypes.POINTER(ctypes.c_double)]),
         "sd_test_graph_linear": (ctypes.c_int, [vp, i32, i64, vp, i32, vp, vp, ctypes.POINTER(ctypes.c_int64), vp,
                                                 vp, i32, vp, vp, i64, i32, i32, i32, vp]),

@@ -445,6 +445,10 @@ __device__ __forceinline__ void gl4t_body(const GLArgs& p, int ncg, int64_t ntil
     // (N = 768: 5.9 MB of split weights for all 10 types did not fit a 4 MB L2 when every XCD
     // walked every node: 196 MB fetched per launch for ~45 MB of operands)
     const int cg = (int)(u % ncg);
+    // a paired launch (GLArgs::pair_n): the upper half of the column groups is the second layer,
+    // with its own weight scale (the f16 hi / lo values depend on it)
+    const bool second = p.pair_n && 2 * cg >= ncg;  // workgroup-uniform
+    const float unscale = second ? p.wsp_unscale2 : p.wsp_unscale;
     const int64_t nrg = (ntile_r + NWV * RT - 1) / (NWV * RT);
     const int j = (int)((u / ncg) / nrg);
     const int64_t rgi = (u / ncg) % nrg;
@@ -652,7 +656,7 @@ __device__ __forceinline__ void gl4t_body(const GLArgs& p, int ncg, int64_t ntil
         const bool oor = PREC != 2 && __builtin_amdgcn_ballot_w64(arow[rt] < p.B && amx[rt] >= 65504.0f) != 0;
         float sc[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) sc[r] = p.wsp_unscale;
+        for (int r = 0; r < 16; ++r) sc[r] = unscale;
         if (RMS) {
             const float t = ss[rt] + __shfl_xor(ss[rt], 32);
 #pragma unroll
@@ -684,7 +688,12 @@ __device__ __forceinline__ void gl4t_body(const GLArgs& p, int ncg, int64_t ntil
 #pragma nounroll
             for (int ct = 0; ct < CT; ++ct) {
                 const int col = (cg * CT + ct) * 32;
-                store_tile(ct, exact_tile_f32(p, row0[rt], j, col), p.bias ? p.bias[p.wrow[j] + col + l32] : 0.f);
+                // (a paired launch: the tile's own layer -- its f32 weights, pair_n columns, its scale)
+                const floatx16 ex = exact_tile_f32_impl(p.x1, p.x1_rs, p.K1, p.x1_div, p.x1_row0, p.x1_blk, p.x2, p.x2_rs, p.K2,
+                                                        p.x2_blk, p.B, p.J, second ? p.W2 : p.W,
+                                                        p.pair_n ? p.wrow[j] >> 1 : p.wrow[j], p.pair_n ? p.pair_n : p.N,
+                                                        unscale, row0[rt], j, second ? col - p.pair_n : col);
+                store_tile(ct, ex, p.bias ? p.bias[p.wrow[j] + col + l32] : 0.f);
             }
         }
     }
@@ -1064,7 +1073,8 @@ __device__ __forceinline__ void gl4_body(const GLArgs& p, const int bx, const in
                 static_assert(MODE != 2 || COLS == 32, "MODE 2: one 32-column tile");
                 const int cc = (q % C4) * 4, r = (q / C4) & 15, j = q / (16 * C4);
                 dst = sY + j * YS + r * YR + cc;
-                return p.zs + zs_off(row0 + 16 * slab + r, j, c0 + cc, J, p.N);
+                // (a paired launch: this layer's columns of the wider scratch, GLArgs::zs_n / zs_c0)
+                return p.zs + zs_off(row0 + 16 * slab + r, j, p.zs_c0 + c0 + cc, J, p.zs_n ? p.zs_n : p.N);
             } else {
                 const int cc = (q & 7) * 4, rr = (q >> 3) & 7, j = (q >> 6) % J, ct = (q >> 6) / J;
                 dst = sY + j * YS8 + rr * COLS + 32 * ct + cc;
@@ -1517,6 +1527,21 @@ __global__ __launch_bounds__(NW * 64, 1) void k_gl4(const GLArgs p) {
     gl4_body<J, NW, RT, CT, RMS, MODE, PREC, STG>(p, blockIdx.x, gridDim.x, smem);
 }
 
+// Mixing phase (MODE 2) of two layers whose GEMM phase ran as one paired k_gl4t launch: per row
+// tile the a.N / 32 column tiles of layer a, then the b.N / 32 of layer b, two 16-row slabs each.
+// The workgroup's tile selects the layer -- its G-hat, FiLM row, activation, LayerNorm affine,
+// residual and output -- and runs that layer's own MODE 2 body on the block index it has in a
+// launch of its own.
+template <int J, int PREC>
+__global__ __launch_bounds__(512, 1) void k_gl4_pair(const GLArgs a, const GLArgs b) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int nta = a.N >> 5, ntb = b.N >> 5;
+    const int L = blockIdx.x >> 1, slab = blockIdx.x & 1;
+    const int pt = L % (nta + ntb), tr = L / (nta + ntb);
+    if (pt < nta) gl4_body<J, 8, 1, 1, false, 2, PREC, 0>(a, ((tr * nta + pt) << 1) | slab, gridDim.x, smem);
+    else gl4_body<J, 8, 1, 1, false, 2, PREC, 0>(b, ((tr * ntb + pt - nta) << 1) | slab, gridDim.x, smem);
+}
+
 // v4 weight staging (GLArgs::gl4_stage): 0 = LDS-DMA stages, 1 = register-staged stages (2, a
 // round-2 diagnostic setting, is now the same as 0: every launch takes its exact LDS).  Process
 // default SKELDIFF_GL4_STAGE for new plans.
@@ -1625,6 +1650,14 @@ static int split_route(const GLArgs& a, bool attn) {
     return (a.J == 17 || a.J == 21) ? 2 : 0;
 }
 
+// the split route launch_graph_linear_v4 gives the layer `a` (0 / 1 / 2 as split_route), for
+// callers that shape work by it before they launch (the row chains' boundaries)
+int graph_linear_split_route(const GLArgs& a) {
+    if (!a.wsp || (a.K1 + a.K2) % 32 || a.K1 % 16 || (a.x1_blk && a.x1_div != 1)) return 0;
+    if (a.J != 16 && a.J != 17 && a.J != 21) return 0;
+    return split_route(a, false);
+}
+
 template <bool ROWMAJOR, int PF>
 static void launch_gl4y_pf(const GLArgs& a, bool rms, int ntc, int64_t ntile_r, const YOut& yo, dim3 grid, hipStream_t s) {
     if (a.prec == 1) {
@@ -1718,16 +1751,18 @@ static hipError_t launch_gl4t(const GLArgs& a, bool rms, int64_t ntile_r, const 
 #define SD_GL4T_PF6 2
 #endif
     constexpr int PFB = ROWMAJOR ? 2 : SD_GL4T_PF, PF6 = ROWMAJOR ? 2 : SD_GL4T_PF6;
-    if (!ROWMAJOR && SD_GL4T_RT2 && a.prec != 2 && a.N <= 192 && a.N % 96 == 0) {
+    // a paired launch (GLArgs::pair_n) takes the form of its layers, with twice the column groups
+    const int Nt = a.pair_n ? a.pair_n : a.N;
+    if (!ROWMAJOR && SD_GL4T_RT2 && a.prec != 2 && Nt <= 192 && Nt % 96 == 0) {
         if (K == 192) return launch_gl4t_v<3, 12, ROWMAJOR, 2, PFB>(a, rms, ntile_r, yo, s);
         if (K == 256) return launch_gl4t_v<3, 16, ROWMAJOR, 2, PFB>(a, rms, ntile_r, yo, s);
         if (K == 384) return launch_gl4t_v<3, 24, ROWMAJOR, 2, PFB>(a, rms, ntile_r, yo, s);
     }
-    if (a.N % 192 == 0) {
+    if (Nt % 192 == 0) {
         if (K == 192) return launch_gl4t_v<6, 12, ROWMAJOR, 1, PF6>(a, rms, ntile_r, yo, s);
         if (K == 256) return launch_gl4t_v<6, 16, ROWMAJOR, 1, PF6>(a, rms, ntile_r, yo, s);
         if (K == 384) return launch_gl4t_v<6, 24, ROWMAJOR, 1, PF6>(a, rms, ntile_r, yo, s);
-    } else if (a.N % 96 == 0) {
+    } else if (Nt % 96 == 0) {
         if (K == 192) return launch_gl4t_v<3, 12, ROWMAJOR, 1>(a, rms, ntile_r, yo, s);
         if (K == 384) return launch_gl4t_v<3, 24, ROWMAJOR, 1>(a, rms, ntile_r, yo, s);
     }
@@ -1759,6 +1794,57 @@ static hipError_t gl4_split_dispatch(const GLArgs& a, bool rms, bool attn, int r
         case 17: return gl4_split<17>(a, rms, attn, route, s);
         case 21: return gl4_split<21>(a, rms, attn, route, s);
         default: return hipErrorNotSupported;
+    }
+}
+
+// ---- paired launch: two sibling layers over one input (final_res_block) ------------------------
+// res_linear and block1 of the final ResnetBlock both read cat(x, r) (K = 384, N = 192).  As two
+// layers the second GEMM phase reads the whole input again and the block costs four dependent
+// launches; as a pair the GEMM phase is one k_gl4t launch over 2 N columns (the column groups of a
+// row group are consecutive u on one XCD: x reaches that L2 once) and the mixing phase one launch
+// over both layers' column tiles.  Per accumulator element nothing changes (the same fragments,
+// scale, bias and MFMA sequence), so the results are bitwise those of the two launches.
+template <int J>
+static hipError_t gl4_pair(const GLArgs& pr, const GLArgs& a, const GLArgs& b, hipStream_t s) {
+    const int64_t ntile_r = (pr.B + 31) / 32;
+    const YOut yo{pr.zs, 32, 1024, (int64_t)(pr.N / 32) * J * 1024, (int64_t)J * 1024};  // as gl4_split, 2 N wide
+    const hipError_t e = launch_gl4t<false>(pr, false, ntile_r, yo, s);
+    if (e != hipSuccess) return e;
+    const dim3 grid((unsigned)((a.N + b.N) / 32 * ntile_r * 2));
+    const size_t lds = ((size_t)J * (16 * 36 + 16) + (size_t)J * J + 64) * sizeof(float);  // gl4_launch_t's MODE 2, CT = 1
+    static_assert((J * (16 * 36 + 16) + J * J + 64) * sizeof(float) <= 64 * 1024, "default dynamic LDS");
+    g_route_bits |= kRouteMixPhase;
+    if (pr.prec == 2) hipLaunchKernelGGL((k_gl4_pair<J, 2>), grid, dim3(512), lds, s, a, b);
+    else hipLaunchKernelGGL((k_gl4_pair<J, 0>), grid, dim3(512), lds, s, a, b);
+    return hipGetLastError();
+}
+
+bool graph_linear_pair_ok(const GLArgs& pr, const GLArgs& a, const GLArgs& b) {
+    if (a.J != 16 && a.J != 17 && a.J != 21) return false;
+    const int K = a.K1 + a.K2;
+    if (!pr.wsp || !a.wsp || !b.wsp || !pr.pair_n || a.N != pr.pair_n || b.N != pr.pair_n || pr.N != 2 * pr.pair_n ||
+        pr.wsp_nct * 32 != pr.N || a.N % 192 || (K != 192 && K != 384))
+        return false;
+    for (const GLArgs* g : {&a, &b}) {  // launch_graph_linear_v4's conditions, the same operands
+        if (((uintptr_t)g->out & 15) || ((uintptr_t)g->res & 15) || (g->res && (g->res_rs & 3)) || (g->out_rs & 3)) return false;
+        if (g->x1 != pr.x1 || g->x2 != pr.x2 || g->K1 != pr.K1 || g->K2 != pr.K2 || g->B != pr.B || g->zs != pr.zs ||
+            g->x1_div != pr.x1_div || g->x1_row0 != pr.x1_row0 || g->x1_blk != pr.x1_blk || g->x2_blk != pr.x2_blk ||
+            g->x1_bf16 != pr.x1_bf16 || g->x2_bf16 != pr.x2_bf16 || g->prec != pr.prec || g->zs_n != pr.N)
+            return false;
+    }
+    if (a.zs_c0 != 0 || b.zs_c0 != a.N) return false;
+    if (K % 32 || a.K1 % 16 || (a.x1_blk && a.x1_div != 1)) return false;
+    // the tiled split route for both layers, as each would take alone, and room for 2 N columns of Y
+    return split_route(a, false) == 2 && split_route(b, false) == 2 && split_route(pr, false) == 2;
+}
+
+hipError_t launch_graph_linear_pair_v4(const GLArgs& pr, const GLArgs& a, const GLArgs& b, hipStream_t s) {
+    if (!graph_linear_pair_ok(pr, a, b)) return hipErrorNotSupported;
+    if (pr.B <= 0) return hipSuccess;
+    switch (a.J) {
+        case 16: return gl4_pair<16>(pr, a, b, s);
+        case 17: return gl4_pair<17>(pr, a, b, s);
+        default: return gl4_pair<21>(pr, a, b, s);
     }
 }
 

@@ -75,6 +75,16 @@ struct GLArgs {
     // v5 only (J > 21): run the GEMM phase alone and leave the pre-mix Y in `out` (k_attention_mix
     // mixes the to_qkv layer); hipErrorNotSupported where the route cannot
     int skip_mix = 0;
+    // v4 tiled split route, two sibling layers over one input in one launch per phase
+    // (launch_graph_linear_pair_v4).  GEMM phase (the pair's args): N = 2 pair_n columns, the
+    // weight fragments and biases of both layers side by side; the column groups of the second
+    // half take its own scale wsp_unscale2 and, on the exact-f32 fallback, its weights W2.
+    // Mixing phase (each layer's own args): its Y is columns zs_c0 .. zs_c0 + N - 1 of a scratch
+    // zs_n columns wide (0: N).
+    int pair_n = 0;
+    const float* W2 = nullptr;
+    float wsp_unscale2 = 1.f;
+    int zs_n = 0, zs_c0 = 0;
 };
 int diag_flags();  // SKELDIFF_DIAG (sd_plan.hip)
 
@@ -149,7 +159,13 @@ hipError_t launch_gemm_split(const GLArgs& a, bool rms, float* z, int64_t z_rs, 
 int graph_linear_variant();
 int gl4_tile_default();
 int gl4_stage_default();
-int64_t split_rows_default();         // SKELDIFF_SPLIT_ROWS: auto split route at or below this many rows
+int graph_linear_split_route(const GLArgs& a);  // v4 route of a layer: 0 one-kernel, 1 k_gl4y, 2 k_gl4t phases
+// Layers a and b (same x1 | x2, K and N, no RMS) on the tiled split route as one k_gl4t launch
+// over pr (N = 2 a.N: GLArgs::pair_n) and one mixing launch; bitwise equal to launching a and b
+// one after the other.  graph_linear_pair_ok: whether the pair launches (else launch a and b).
+bool graph_linear_pair_ok(const GLArgs& pr, const GLArgs& a, const GLArgs& b);
+hipError_t launch_graph_linear_pair_v4(const GLArgs& pr, const GLArgs& a, const GLArgs& b, hipStream_t s);
+int64_t split_rows_default();       // SKELDIFF_SPLIT_ROWS: auto split route at or below this many rows
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
 hipError_t launch_update(const UpdArgs& a, hipStream_t s);
 hipError_t launch_mix_mfma(const float* z, const float* G, float* out, int64_t rows, int J, int N, bool transpose,

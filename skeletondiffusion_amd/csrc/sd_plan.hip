@@ -178,6 +178,12 @@ struct sd_plan {
     std::vector<GL> qkv, outp;     // attention (or single GL when use_attention == 0)
     std::vector<bool> has_attn;
     GL fres_res, fglin;
+    // final_res_block's res_linear and block1 (r1.back()) as one GEMM-phase launch over the input
+    // they share (sd::launch_graph_linear_pair_v4): N = 2 H, both layers' weight fragments side by
+    // side, pair_bias (types, 2 H) with zeros for res_linear; pair_ok: built at finalize
+    GL fres_pair;
+    float* pair_bias = nullptr;
+    bool pair_ok = false;
     int t1w = -1, t1b = -1, t3w = -1, t3b = -1;
     int s_c1 = -1, s_c2 = -1, s_lv = -1, s_u = -1;
 
@@ -555,13 +561,31 @@ int run_denoiser(const sd_plan* p, const float* x_t, const float* x_cond, int64_
     const float* film = p->film + ((size_t)L * p->T + t) * 2 * H;
     a = gl_args(p, p->fres_res, w.x, 1, w.r, nullptr, nullptr, w.res, rows);
     lay(a, 1, 1, 1);
-    SD_LAUNCH(prof, 0, sd::launch_graph_linear(a, false, s));
+    sd::GLArgs b1 = gl_args(p, p->r1[L], w.x, 1, w.r, film, nullptr, w.h, rows);
+    lay(b1, 1, 1, 1);
+    b1.act = 1;
+    // res_linear and block1 read the same input: on the tiled split route one GEMM-phase and one
+    // mixing launch for both (sd_graph_linear_v4.hip, paired launch), else one layer after the other
+    bool paired = false;
+    if (p->pair_ok && (p->variant == 0 || p->variant == 4)) {
+        sd::GLArgs pr = gl_args(p, p->fres_pair, w.x, 1, w.r, nullptr, nullptr, nullptr, rows);
+        lay(pr, 1, 1, 1);
+        pr.bias = p->pair_bias;
+        pr.pair_n = a.N;
+        pr.W2 = p->r1[L].wuse;
+        pr.wsp_unscale2 = b1.wsp_unscale;
+        sd::GLArgs pa = a, pb = b1;
+        pa.zs_n = pb.zs_n = pr.N;
+        pb.zs_c0 = a.N;
+        if (sd::graph_linear_pair_ok(pr, pa, pb)) {
+            SD_LAUNCH(prof, 0, sd::launch_graph_linear_pair_v4(pr, pa, pb, s));
+            paired = true;
+        }
+    }
+    if (!paired) SD_LAUNCH(prof, 0, sd::launch_graph_linear(a, false, s));
     if ((rc = snap(a))) return rc;
-    a = gl_args(p, p->r1[L], w.x, 1, w.r, film, nullptr, w.h, rows);
-    lay(a, 1, 1, 1);
-    a.act = 1;
-    SD_LAUNCH(prof, 0, sd::launch_graph_linear(a, false, s));
-    if ((rc = snap(a))) return rc;
+    if (!paired) SD_LAUNCH(prof, 0, sd::launch_graph_linear(b1, false, s));
+    if ((rc = snap(b1))) return rc;
     a = gl_args(p, p->r2[L], w.h, 1, nullptr, nullptr, w.res, w.res, rows);
     lay(a, 1, 1, 1);
     a.act = 1;
@@ -866,7 +890,43 @@ int sd_plan_finalize(sd_plan* p, void* stream_) {
     }
     if ((rc = pack_gl(p->fres_res))) return rc;
     if ((rc = pack_gl(p->fglin))) return rc;
-    p->fuse_ok = p->d.use_attention && (J <= 17 || J == 21) && p->d.attn_dim_head == 32;
+    {
+        // the pair's B fragments: per (type, chunk) the column tiles of res_linear, then block1's
+        // (make_split_weights layout [type][chunk][tile][1024 halves]; unpadded: nct * 32 == N), each
+        // layer's values under its own scale
+        const GL &ga = p->fres_res, &gb = p->r1.back();
+        GL& pr = p->fres_pair;
+        if (ga.K1 == gb.K1 && ga.K2 == gb.K2 && ga.N == gb.N && !ga.rms && !gb.rms && ga.split.w && gb.split.w &&
+            ga.split_bf.w && gb.split_bf.w && ga.split.nct * 32 == ga.N && gb.split.nct == ga.split.nct &&
+            ga.split_bf.nct == ga.split.nct && gb.split_bf.nct == ga.split.nct) {
+            pr.K1 = ga.K1;
+            pr.K2 = ga.K2;
+            pr.N = 2 * ga.N;
+            pr.wuse = ga.wuse;
+            const size_t trows = (size_t)p->ntypes * ((ga.K1 + ga.K2) / 16);
+            const size_t tb = (size_t)ga.split.nct * 1024 * sizeof(_Float16);  // one layer's tiles of a (type, chunk)
+            auto cat = [&](const sd::SplitW& x, const sd::SplitW& y, sd::SplitW* o) -> int {
+                int r = dalloc(p, &o->w, trows * 2 * tb / sizeof(_Float16));
+                if (r) return r;
+                SD_HIP(hipMemcpy2DAsync(o->w, 2 * tb, x.w, tb, tb, trows, hipMemcpyDeviceToDevice, s));
+                SD_HIP(hipMemcpy2DAsync(reinterpret_cast<char*>(o->w) + tb, 2 * tb, y.w, tb, tb, trows, hipMemcpyDeviceToDevice, s));
+                o->nct = 2 * x.nct;
+                o->scale = x.scale;
+                o->unscale = x.unscale;
+                return SD_OK;
+            };
+            if ((rc = cat(ga.split, gb.split, &pr.split))) return rc;
+            if ((rc = cat(ga.split_bf, gb.split_bf, &pr.split_bf))) return rc;
+            const size_t nb = (size_t)ga.N * sizeof(float);
+            if ((rc = dalloc(p, &p->pair_bias, (size_t)p->ntypes * 2 * ga.N))) return rc;
+            SD_HIP(hipMemsetAsync(p->pair_bias, 0, (size_t)p->ntypes * 2 * nb, s));
+            if (ga.b >= 0) SD_HIP(hipMemcpy2DAsync(p->pair_bias, 2 * nb, p->ptr(ga.b), nb, nb, p->ntypes, hipMemcpyDeviceToDevice, s));
+            if (gb.b >= 0)
+                SD_HIP(hipMemcpy2DAsync(p->pair_bias + ga.N, 2 * nb, p->ptr(gb.b), nb, nb, p->ntypes, hipMemcpyDeviceToDevice, s));
+            p->pair_ok = true;
+        }
+    }
+    p->fuse_ok =p->d.use_attention && (J <= 17 || J == 21) && p->d.attn_dim_head == 32;
     for (size_t l = 0; l < p->qkv.size(); ++l)
         if (p->has_attn[l] && !p->qkv[l].split.w) p->fuse_ok = false;
     // row-blocked activations need every graph-linear on v4 (split weights, K multiple of 32)
@@ -1053,6 +1113,46 @@ static int64_t chain_row(int i, int n, int64_t rows, int64_t unit) {
     return i >= n ? rows : std::min(rows, (rows + unit - 1) / unit * i / n * unit);
 }
 
+// Chain boundaries on the tiled route's GEMM tile.  k_gl4t's workgroup covers 256
+// rows at RT = 2 (N <= 192) and 128 at RT = 1 (to_qkv), and a tile past the chain's rows still
+// loads and multiplies (gl4t_body skips its stores only): cut on 32-row units, 3,200 rows on three
+// chains are 33 / 33 / 34 tiles, 15 row groups of 256 where 12.5 hold data.  On kChainTileUnit
+// rows the cuts leave whole waves / workgroups to all chains but the last.  Only where every chain
+// keeps two full 256-row workgroups; below that the 32-row cuts stay (so do the small batches'
+// chain shapes).  Rows are independent and the Philox rows / x_cond phase follow r0, so the
+// results do not depend on where the cuts fall.
+#ifndef SD_CHAIN_TILE_UNIT
+#define SD_CHAIN_TILE_UNIT 128
+#endif
+constexpr int64_t kChainTileUnit = SD_CHAIN_TILE_UNIT;
+static_assert(kChainTileUnit >= 32 && kChainTileUnit % 32 == 0, "chains start on 32-row blocks");
+static int64_t chain_start(int64_t rows, int n, int64_t unit, int i) {
+    if (n < 1) n = 1;
+    if (unit > 32) {
+        if (unit % 32) unit = 32;
+        for (int k = 0; k < n && unit > 32; ++k)
+            if (chain_row(k + 1, n, rows, unit) - chain_row(k, n, rows, unit) < 512) unit = 32;
+    } else {
+        unit = 32;
+    }
+    return chain_row(i, n, rows, unit);
+}
+// whether the graph-linears of a sampling call over `rows` rows take the tiled split route
+// (k_gl4t): the route of a ResnetBlock layer as run_denoiser sets it up (the route follows the
+// whole call's rows, GLArgs::route_rows, not a chain's)
+static bool tiled_route_call(const sd_plan* p, int64_t rows, const WS& w) {
+    if (!p->blocked_now() || p->r1.empty()) return false;
+    sd::GLArgs a = gl_args(p, p->r1[0], w.r, 1, nullptr, nullptr, nullptr, w.h, rows);
+    a.zs = w.qkv;
+    a.zs_cap = (rows + 31) / 32 * 32 * p->J * qkv_width(p);
+    a.route_rows = rows;
+    return sd::graph_linear_split_route(a) == 2;
+}
+int64_t sd_chain_start(int64_t rows, int32_t nchains, int64_t unit, int32_t i) {
+    return rows <= 0 || i <= 0 ? 0 : chain_start(rows, nchains, unit, i);
+}
+int64_t sd_chain_tile_unit(void) { return kChainTileUnit; }
+
 // Creates the auxiliary streams / fork-join events chains 1 .. n-1 use (caller holds cmu).
 // Diagnostics (SKELDIFF_DIAG bit 13): every chain, the first included, on a stream
 // of its own whose CU mask is a disjoint 1/n of the device's CUs (no two chains share a CU).
@@ -1105,8 +1205,8 @@ static int record_loop(const sd_plan* p, const float* x_T, const float* x_cond, 
     const int c0 = only < 0 ? 0 : only, c1 = only < 0 ? nch : only + 1;
     for (int i = c0; i < c1; ++i) {
         Chain& c = ch[i];
-        c.r0 = chain_row(i, nch, rows, unit);
-        c.n = chain_row(i + 1, nch, rows, unit) - c.r0;
+        c.r0 = chain_start(rows, nch, unit, i);
+        c.n = chain_start(rows, nch, unit, i + 1) - c.r0;
         c.w = shift_ws(p, w, c.r0, i);
         c.cur = (dev_start || bf) ? c.w.img1 : x_T + c.r0 * JD;
         if (dev_start) SD_HIP(sd::launch_noise_fill(c.w.img1, c.n, JD, seed, row0, T, rng, cs[i], c.r0, bf));
@@ -1192,6 +1292,7 @@ int sd_sample_loop(const sd_plan* p, const float* x_T, const float* x_cond, int6
     if ((rc = ws_reset(w, s))) return rc;
     int64_t unit = 32;
     const int nch = chain_count(p, rows, cond_repeat, &unit);
+    if (nch > 1 && tiled_route_call(p, rows, w)) unit = kChainTileUnit;  // chain_start: where every chain keeps 512 rows
     mp->last_chains.store(nch);
     std::unique_lock<std::mutex> lk(mp->cmu, std::defer_lock);  // fork/join objects are shared
     hipStream_t cs[sd_plan::kMaxChains];

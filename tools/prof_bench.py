@@ -36,6 +36,8 @@ def kind(name):
         return "gemm_tiled"
     if "k_gl4y" in n:
         return "gemm_wave"
+    if "k_gl4_pair" in n:  # the mixing phase of two layers whose GEMM phase was one paired k_gl4t dispatch
+        return "mix_pair"
     m = re.match(r"sd::k_gl4<(.*)>", n)
     if m:
         args = m.group(1).split(",")
@@ -98,16 +100,17 @@ if pmc:
         wa = avg.get("SQ_WAIT_ANY", 0) / wave * 100 if wave else float("nan")
         lines.append(f"| `{k[:80]}` | {nd} | {rd:.1f} | {wr:.1f} | {mfma:.1f} | {wi:.1f} | {wa:.1f} |")
         kd = kind(k)
-        if kd in ("gemm_tiled", "gemm_wave", "one_kernel", "fused_attention", "mix_phase", "attn_phase"):
+        if kd in ("gemm_tiled", "gemm_wave", "one_kernel", "fused_attention", "mix_phase", "attn_phase", "mix_pair"):
             tot = sum(c.get("FETCH_SIZE", [])) * 2 * 1024 + sum(c.get("WRITE_SIZE", [])) * 1024
             layer_bytes += tot
-            if kd in ("gemm_tiled", "gemm_wave", "one_kernel", "fused_attention"):
+            # (a paired launch is one GEMM-phase dispatch for two layers: its mixing dispatch counts the second)
+            if kd in ("gemm_tiled", "gemm_wave", "one_kernel", "fused_attention", "mix_pair"):
                 layers += len(c.get("FETCH_SIZE", []))
     if layers:
         per = layer_bytes / layers
         lines += ["", f"HBM traffic per graph-linear layer launch: **{per / 1e6:.1f} MB** "
                       f"({layers} layer launches in the FETCH / WRITE passes)."]
-        if b:
+        if b and "roofline" in b:  # the --full line (the plain bench line carries no roofline)
             alg = b["roofline"]["algorithmic_bytes_per_launch"]
             lines.append(f"Algorithmic bytes per layer launch: {alg / 1e6:.1f} MB -> traffic / algorithmic = "
                          f"{per / alg:.2f}.")
