@@ -10,6 +10,9 @@ reduction != 'mean'), reduced in a fixed order (deterministic).
     fde(target, pred, t0, t, reduction)  multimodal.py:60-73  min over samples of last-frame L2
 
 Up to 64 samples per sequence (the release evaluation draws 50).
+
+cmd(val_per_frame, val_ref) (multimodal.py:10-13) is the one host-side function here: the CMD score of
+a class's mean motion profile, a sum over at most a few hundred frame steps.
 """
 from __future__ import annotations
 
@@ -135,4 +138,16 @@ def mmfde(target: torch.Tensor, pred: torch.Tensor, mm_gt, t0: int = 0, t: int =
     return _mm(target, pred, mm_gt, t0, t, False)
 
 
-__all__ = ["lat_apd", "apd", "ade", "fde", "mmade", "mmfde"]
+def cmd(val_per_frame, val_ref) -> float:
+    """Cumulative motion distribution of one class (multimodal.py:10-13): val_per_frame the class's
+    mean motion profile M_t (frames - 1 values: array, list or tensor), val_ref its dataset mean
+    motion M: sum_t (T - t) |M_t - M|.  The class-weighted aggregation over a dataset
+    (src/metrics/cmd.py:15-31) stays with the caller, on the host."""
+    import numpy as np
+
+    v = np.asarray(val_per_frame.detach().cpu() if torch.is_tensor(val_per_frame) else val_per_frame, dtype=np.float64)
+    T = len(v) + 1
+    return float(np.sum((T - np.arange(1, T)) * np.abs(v - float(val_ref))))
+
+
+__all__ = ["lat_apd", "apd", "ade", "fde", "mmade", "mmfde", "cmd"]
