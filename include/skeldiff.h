@@ -253,6 +253,26 @@ int sd_best_of_k_backward(const float* dloss_sel, const int64_t* idx, int64_t ns
 int sd_pose_loss(const float* pred, const float* target, int64_t nseq, int32_t samples, int32_t frames,
                  int32_t joints, int32_t dims, int32_t mse, float* per_sample, void* stream);
 
+/* Best-sample selection (reference src/metrics/utils.py:12-30 choose_best_sample / get_best_sample_idx,
+ * src/metrics/multimodal.py:37-42 mpjpe, src/eval_utils.py:59-62 the long-term rollout's pick):
+ * pred (nseq, samples, frames, joints, coords), target (nseq, frames, joints, coords), f32, dense,
+ * 4-byte aligned (16-byte loads are used wherever the addresses allow).
+ *   per_sample (nseq, samples)  d[b, s] = mean over frames and joints of the per-joint L2 distance
+ *                               ||pred[b, s, t, j, :] - target[b, t, j, :]||; required: the selection
+ *                               reads it.  One workgroup per (sequence, sample), pred read once,
+ *                               a fixed summation order that does not depend on s or on alignment.
+ *   idx_out (nseq) int64        the index of the smallest d[b, :] (torch.min(dim).indices: the first
+ *                               minimum; the first NaN if any), as sd_best_of_k
+ *   min_out (nseq)              d[b, idx[b]] (mpjpe)
+ *   best_out (nseq, frames, joints, coords)       pred[b, idx[b]]
+ *   tail_out (nseq, tail_frames, joints, coords)  pred[b, idx[b], frames - tail_frames:] (the next
+ *                               observation of the rollout); non-NULL only with tail_frames > 0
+ * Every output but per_sample may be NULL.  1 <= samples <= 64, coords == 3, frames, joints >= 1,
+ * 0 <= tail_frames <= frames (SD_E_INVALID names the argument); nseq == 0 launches nothing. */
+int sd_best_sample(const float* pred, const float* target, int64_t nseq, int32_t samples, int32_t frames,
+                   int32_t joints, int32_t coords, int32_t tail_frames, float* per_sample, float* min_out,
+                   int64_t* idx_out, float* best_out, float* tail_out, void* stream);
+
 /* Test hooks: one kernel on caller buffers, for the per-kernel numerics tests.
  * sd_test_graph_linear: out(B,J,N) = act(FiLM(ghat @ (s_j W[type j] [x1_j | x2_j] + bias[type j]))) + res,
  *   W (types,N,K1+K2), bias (types,N) or NULL, ghat (J,J), film (2N) or NULL, res (B,J,N) or NULL,

@@ -202,6 +202,13 @@ hipError_t launch_best_of_k_bwd(const float* dsel, const int64_t* idx, int64_t n
 hipError_t launch_pose_loss(const float* pred, const float* target, int64_t nseq, int S, int T, int J, int C, int mse,
                             float* out, hipStream_t s);
 
+// best-sample selection (sd_metrics.hip; metrics/utils.py:12-30, multimodal.py:37-42): per (sequence,
+// sample) the mean per-joint L2 distance to the target, then per sequence the first minimum, its
+// distance and the gathered trajectory / its last tail_frames frames (each output but d nullable)
+hipError_t launch_best_sample(const float* pred, const float* target, int64_t nseq, int S, int T, int J,
+                              int tail_frames, float* d, float* min_out, int64_t* idx_out, float* best_out,
+                              float* tail_out, hipStream_t s);
+
 // plan-finalize helpers (one-time)
 hipError_t launch_sinusoidal(float* emb, int T, int dim, float neg_scale, hipStream_t s);
 hipError_t launch_linear(const float* x, int M, int K, const float* W, const float* b, int N,

@@ -8,11 +8,16 @@
 //   mmade / mmfde: the same minimum against each of a sequence's multimodal ground truths,
 //             averaged over them (multimodal.py:108-135): one workgroup per (sequence, gt) pair,
 //             then a fixed-order mean per sequence.
+//   best sample: per (sequence, sample) the mean per-joint L2 distance to the target (mpjpe,
+//             multimodal.py:37-42), one workgroup per pair; then per sequence the first minimum and
+//             the gather of that sample (metrics/utils.py:12-30) -- see k_sample_dist below.
 // Samples are (S, X) rows of one sequence, X = T_frames * F (flattened frame-major, as
 // `pred.reshape(batch, n_samples, seq_length, -1)`).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+
+#include <algorithm>
 
 #include "sd_internal.h"
 
@@ -214,7 +219,170 @@ __global__ __launch_bounds__(256) void k_pose_loss(const float* __restrict__ pre
     if (lane == 0) out[w] = acc / (float)T;
 }
 
+// ---- best-sample selection (reference metrics/utils.py:12-30 choose_best_sample / get_best_sample_idx,
+// multimodal.py:37-42 mpjpe, eval_utils.py:59-62 the long-term rollout's selection) -----------------
+// d[b, s] = mean over frames and joints of ||pred[b, s, t, j, :] - target[b, t, j, :]||_2.
+//
+// Layout.  One workgroup per (sequence, sample) pair; a sample's block is N = T * J joints = L = 3 N
+// floats.  The block is cut into groups of 4 joints (12 floats) by joint index alone: thread `tid`
+// takes the groups tid, tid + 256, ...  A group is read with 16-byte loads: three when the block
+// starts on a 16-byte boundary, else the four aligned quads that cover it (the block starts A = 1..3
+// floats past a boundary; a group starts a multiple of 4 floats into the block, so A is the same for
+// all of them).  A group whose quads would reach outside the block -- the first one of a misaligned
+// block, the last one or two -- is read float by float.  pred and target have an A each.
+//
+// Summation order.  It depends on the joint index only, never on the alignment or the sample index:
+// a joint's distance is sqrt(fma(dz, dz, fma(dy, dy, dx dx))); a group's four distances are added in
+// joint order in f32; a thread adds its groups in f64 in group order; the 64 lanes' sums meet in an
+// xor butterfly (f64) and the 4 waves' as (w0 + w1) + (w2 + w3).  So two samples with the same bytes
+// get the same bits, and no f32 chain is longer than 4 terms.
+template <int A>
+__device__ __forceinline__ void load12(const float* __restrict__ blk, int64_t e0, int64_t L, float (&v)[12]) {
+    constexpr int Q = A ? 4 : 3;
+    const int64_t ws = e0 - A;  // on a 16-byte boundary (e0 % 4 == 0)
+    if (ws >= 0 && ws + 4 * Q <= L) {
+        const float4* q = reinterpret_cast<const float4*>(blk + ws);
+        float w[4 * Q];
+#pragma unroll
+        for (int k = 0; k < Q; ++k) {
+            const float4 x = q[k];
+            w[4 * k] = x.x;
+            w[4 * k + 1] = x.y;
+            w[4 * k + 2] = x.z;
+            w[4 * k + 3] = x.w;
+        }
+#pragma unroll
+        for (int i = 0; i < 12; ++i) v[i] = w[i + A];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 12; ++i) v[i] = e0 + i < L ? blk[e0 + i] : 0.f;
+    }
+}
+
+__device__ __forceinline__ void load12(int A, const float* __restrict__ blk, int64_t e0, int64_t L, float (&v)[12]) {
+    switch (A) {  // the same in every thread of the workgroup
+        case 0: load12<0>(blk, e0, L, v); break;
+        case 1: load12<1>(blk, e0, L, v); break;
+        case 2: load12<2>(blk, e0, L, v); break;
+        default: load12<3>(blk, e0, L, v); break;
+    }
+}
+
+// floats past the previous 16-byte boundary (p is 4-byte aligned)
+__device__ __forceinline__ int quad_phase(const float* p) { return (int)(((uintptr_t)p >> 2) & 3); }
+
+__global__ __launch_bounds__(256) void k_sample_dist(const float* __restrict__ pred,
+                                                     const float* __restrict__ target, int64_t pairs, int S,
+                                                     int64_t N, float* __restrict__ d) {
+    __shared__ double wsum[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t L = 3 * N, groups = (N + 3) / 4;
+    for (int64_t w = blockIdx.x; w < pairs; w += gridDim.x) {
+        const float* p = pred + w * L;
+        const float* tg = target + (w / S) * L;
+        const int ap = quad_phase(p), at = quad_phase(tg);
+        double acc = 0.0;
+        for (int64_t g = tid; g < groups; g += 256) {
+            float pv[12], tv[12];
+            load12(ap, p, 12 * g, L, pv);
+            load12(at, tg, 12 * g, L, tv);
+            float s4 = 0.f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float dx = pv[3 * k] - tv[3 * k], dy = pv[3 * k + 1] - tv[3 * k + 1],
+                            dz = pv[3 * k + 2] - tv[3 * k + 2];
+                const float dn = sqrtf(fmaf(dz, dz, fmaf(dy, dy, dx * dx)));
+                if (4 * g + k < N) s4 += dn;
+            }
+            acc += (double)s4;
+        }
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+        if (lane == 0) wsum[wave] = acc;
+        __syncthreads();
+        if (tid == 0) d[w] = (float)(((wsum[0] + wsum[1]) + (wsum[2] + wsum[3])) / (double)N);
+        __syncthreads();
+    }
+}
+
+// dst[0, n) = src[0, n) by the threads t0, t0 + nt, ...: 16-byte stores from dst's first 16-byte
+// boundary on, fed by 16-byte loads where src is on a boundary there too, else by four floats
+__device__ __forceinline__ void copy_span(float* __restrict__ dst, const float* __restrict__ src, int64_t n,
+                                          int64_t t0, int64_t nt) {
+    const int64_t head = min(n, (int64_t)((4 - quad_phase(dst)) & 3));
+    const int64_t quads = (n - head) / 4;
+    for (int64_t e = t0; e < head; e += nt) dst[e] = src[e];
+    float4* dq = reinterpret_cast<float4*>(dst + head);
+    if (quad_phase(src + head) == 0) {
+        const float4* sq = reinterpret_cast<const float4*>(src + head);
+        for (int64_t q = t0; q < quads; q += nt) dq[q] = sq[q];
+    } else {
+        for (int64_t q = t0; q < quads; q += nt) {
+            const float* sp = src + head + 4 * q;
+            dq[q] = make_float4(sp[0], sp[1], sp[2], sp[3]);
+        }
+    }
+    for (int64_t e = head + 4 * quads + t0; e < n; e += nt) dst[e] = src[e];
+}
+
+// Per sequence the index of the smallest distance (torch.min(dim).indices as k_best_of_k: the first
+// minimum, the first NaN if there is one), that distance, and the selected sample's block of L
+// floats / its last Lt floats.  Workgroup (b, c): sequence b, share c of the copies; c = 0 writes
+// the index and the distance.
+__global__ __launch_bounds__(256) void k_best_select(const float* __restrict__ pred, const float* __restrict__ d,
+                                                     int S, int64_t L, int64_t Lt, float* __restrict__ min_out,
+                                                     int64_t* __restrict__ idx_out, float* __restrict__ best_out,
+                                                     float* __restrict__ tail_out) {
+    __shared__ float dv[kMaxSamples];
+    __shared__ int sel;
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    if (tid < S) dv[tid] = d[b * S + tid];
+    __syncthreads();
+    if (tid == 0) {
+        int best = 0;
+        float bv = dv[0];
+        for (int j = 1; j < S; ++j) {
+            const float x = dv[j];
+            if (bv != bv) break;  // a NaN already selected: the first NaN wins
+            if (x != x || x < bv) {
+                best = j;
+                bv = x;
+            }
+        }
+        sel = best;
+        if (blockIdx.y == 0) {
+            if (idx_out) idx_out[b] = best;
+            if (min_out) min_out[b] = bv;
+        }
+    }
+    __syncthreads();
+    const float* src = pred + (b * S + sel) * L;
+    const int64_t t0 = (int64_t)blockIdx.y * 256 + tid, nt = (int64_t)gridDim.y * 256;
+    if (best_out) copy_span(best_out + b * L, src, L, t0, nt);
+    if (tail_out) copy_span(tail_out + b * Lt, src + (L - Lt), Lt, t0, nt);
+}
+
 }  // namespace
+
+hipError_t launch_best_sample(const float* pred, const float* target, int64_t nseq, int S, int T, int J,
+                              int tail_frames, float* d, float* min_out, int64_t* idx_out, float* best_out,
+                              float* tail_out, hipStream_t s) {
+    if (nseq <= 0) return hipSuccess;
+    if (S < 1 || S > kMaxSamples || T < 1 || J < 1 || tail_frames < 0 || tail_frames > T || nseq > INT32_MAX || !d)
+        return hipErrorInvalidValue;
+    const int64_t pairs = nseq * S, N = (int64_t)T * J, L = 3 * N, Lt = 3 * (int64_t)tail_frames * J;
+    hipLaunchKernelGGL(k_sample_dist, dim3((unsigned)std::min(pairs, (int64_t)1 << 30)), dim3(256), 0, s, pred, target, pairs,
+                       S, N, d);
+    if (!tail_frames) tail_out = nullptr;
+    if (min_out || idx_out || best_out || tail_out) {
+        // 2 quads per thread and share; the copies of one sequence are at most a few hundred KB
+        const int64_t span = std::max(best_out ? L : (int64_t)0, tail_out ? Lt : (int64_t)0);
+        const unsigned shares = (unsigned)std::min(std::max((span + 2047) / 2048, (int64_t)1), (int64_t)32);
+        hipLaunchKernelGGL(k_best_select, dim3((unsigned)nseq, shares), dim3(256), 0, s, pred, d, S, L, Lt, min_out,
+                           idx_out, best_out, tail_out);
+    }
+    return hipGetLastError();
+}
 
 hipError_t launch_best_of_k(const float* sim, const float* loss, int64_t nseq, int k, int64_t* idx, float* sel,
                             hipStream_t s) {

@@ -1513,6 +1513,26 @@ int sd_pose_loss(const float* pred, const float* target, int64_t nseq, int32_t s
     return SD_OK;
 }
 
+int sd_best_sample(const float* pred, const float* target, int64_t nseq, int32_t samples, int32_t frames,
+                   int32_t joints, int32_t coords, int32_t tail_frames, float* per_sample, float* min_out,
+                   int64_t* idx_out, float* best_out, float* tail_out, void* stream) {
+    if (nseq < 0 || nseq > INT32_MAX) return fail(SD_E_INVALID, "best_sample: nseq must be in 0..2^31-1");
+    if (samples < 1 || samples > 64) return fail(SD_E_INVALID, "best_sample: samples must be in 1..64");
+    if (coords != 3) return fail(SD_E_INVALID, "best_sample: coords must be 3");
+    if (frames < 1) return fail(SD_E_INVALID, "best_sample: frames must be >= 1");
+    if (joints < 1) return fail(SD_E_INVALID, "best_sample: joints must be >= 1");
+    if (tail_frames < 0 || tail_frames > frames)
+        return fail(SD_E_INVALID, "best_sample: tail_frames must be in 0..frames");
+    if (tail_out && tail_frames == 0) return fail(SD_E_INVALID, "best_sample: tail_out given with tail_frames = 0");
+    if (nseq == 0) return SD_OK;
+    if (!pred) return fail(SD_E_INVALID, "best_sample: pred is null");
+    if (!target) return fail(SD_E_INVALID, "best_sample: target is null");
+    if (!per_sample) return fail(SD_E_INVALID, "best_sample: per_sample is required (it is the workspace)");
+    SD_HIP(sd::launch_best_sample(pred, target, nseq, samples, frames, joints, tail_frames, per_sample, min_out, idx_out,
+                                  best_out, tail_out, (hipStream_t)stream));
+    return SD_OK;
+}
+
 // kernel generation / v4 tile of the sd_test_* hooks only (plans take theirs from SD_OPT_*)
 static int g_test_variant = -1, g_test_tile = -1;  // -1: the process defaults (SKELDIFF_* at load)
 static int test_variant() { return g_test_variant >= 0 ? g_test_variant : sd::graph_linear_variant(); }

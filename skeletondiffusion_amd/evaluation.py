@@ -1,0 +1,135 @@
+"""The reference's evaluation chain on the HIP engine: `get_prediction` (src/eval_prepare_model.py:89-121)
+and the long-term rollouts (src/eval_utils.py:44-99), with the reference's signatures and return values.
+
+    get_diffusion_latent_codes(obs, model, num_samples, ...)   past embedding -> sample()
+    decode_latent_pred(obs, latent_pred, z_past, model, ...)   latents -> (B, S, pred_length, J, 3)
+    get_prediction(obs, model, num_samples, pred_length, ...)  the two in a row
+    long_term_prediction_best_every50(...)   draw S futures, keep the one closest to the ground truth,
+                                             feed its last observed-length frames back, repeat
+    long_term_prediction_best_first50(...)   draw S futures once, then continue each of them
+
+`model` is the (autoencoder, diffusion) pair of `prepare_model`.  Every stage is a HIP kernel sequence
+(sd_gru_encode, sd_sample_loop, sd_gru_decode, sd_best_sample); nothing here copies to the host or
+synchronises, so the segments of a rollout queue back to back on the stream.
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+
+from . import metrics
+
+
+def get_diffusion_latent_codes(obs, model, num_samples=50, diffusion_conditioning=True, sampler_kwargs=None, **kwargs):
+    """eval_prepare_model.py:89-104: (latent_pred (bs * num_samples, J, latent), z_past (bs, J, latent)).
+    The conditioning goes to sample() once per sequence: the engine repeats `x_cond` rows that divide
+    the batch (`cond_repeat`), so `repeat_interleave(num_samples, 0)` is never materialised.
+    `sampler_kwargs` may carry the engine's `seed`."""
+    autoencoder, diffusion = model
+    bs = obs.shape[0]
+    sampler_kwargs = sampler_kwargs or {}
+    z_past = autoencoder.get_past_embedding(obs)  # z_activation applied
+    if diffusion_conditioning:
+        latent_pred, _ = diffusion.sample(batch_size=bs * num_samples, x_cond=z_past, **sampler_kwargs)
+    else:  # (the reference reads z_past before assigning it on this branch, :102)
+        latent_pred, _ = diffusion.sample(batch_size=bs * num_samples, **sampler_kwargs)
+    return latent_pred, z_past
+
+
+def decode_latent_pred(obs, latent_pred, z_past, model, num_samples=50, pred_length=100, **kwargs):
+    """eval_prepare_model.py:106-116: (bs, num_samples, pred_length, J, 3).  The decoder reads the last
+    two observed frames only, so only those are repeated per sample; it does not read z_past
+    (decoder.py:85-104)."""
+    autoencoder, _ = model
+    bs, _, j, f = obs.shape
+    pred = autoencoder.decode(obs[:, -2:].repeat_interleave(num_samples, 0), latent_pred, None, ph=pred_length)
+    return pred.view(bs, num_samples, pred_length, j, f)
+
+
+def get_prediction(obs, model, num_samples=50, pred_length=100, diffusion_conditioning=True, sampler_kwargs=None,
+                   **kwargs):
+    """eval_prepare_model.py:118-121: obs (bs, obs_length, J, 3) -> (bs, num_samples, pred_length, J, 3)."""
+    lat_pred, z_past = get_diffusion_latent_codes(obs, model, num_samples=num_samples,
+                                                  diffusion_conditioning=diffusion_conditioning,
+                                                  sampler_kwargs=sampler_kwargs, **kwargs)
+    return decode_latent_pred(obs, lat_pred, z_past, model, num_samples=num_samples, pred_length=pred_length, **kwargs)
+
+
+def process_evaluation_pair(target, pred_dict):
+    """eval_prepare_model.py:124-134 without the skeleton: the shape assertion, and the inputs back.
+    `transform_to_metric_space` stays with the caller (pass a function of your own to the rollouts)."""
+    pred, mm_gt, obs = pred_dict["pred"], pred_dict.get("mm_gt"), pred_dict["obs"]
+    batch_size, n_samples, seq_length, num_joints, features = pred.shape
+    assert features == 3 and list(target.shape) == [batch_size, seq_length, num_joints, features]
+    return target, pred, mm_gt, obs
+
+
+def _segments(config):
+    """(number of segments, frames kept of the last one or None): ceil(factor) segments, the last cut
+    to int(factor * pred_length) % pred_length frames for a fractional factor (eval_utils.py:51-54)."""
+    factor, pred_length = config["long_term_factor"], config["pred_length"]
+    n = math.ceil(factor)
+    return n, (int(factor * pred_length) % pred_length if int(factor) != factor else None)
+
+
+def long_term_prediction_best_every50(data, target, extra, get_prediction, process_evaluation_pair=process_evaluation_pair,
+                                      num_samples=50, config=None):
+    """eval_utils.py:44-67: per segment draw the futures, keep the one closest to the ground truth and
+    take its last observed-length frames as the next past.  Selection, best trajectory and next past
+    come from one `metrics.best_sample` call; nothing between two segments leaves the device.
+    Returns (target, pred, mm_gt, data); pred (B, num_samples, T_total, J, 3) is the best trajectory
+    expanded over the sample axis (a view: the reference's `repeat` of identical rows)."""
+    new_data = data
+    final_pred_data, final_target_data = [], []
+    n_past_frames = data.shape[-3]
+    n_seg, last_frames = _segments(config)
+    pl = config["pred_length"]
+    for idx in range(n_seg):
+        pred = get_prediction(new_data, extra=extra)  # (batch_size, n_samples, seq_length, num_joints, features)
+        if idx == n_seg - 1 and last_frames is not None:
+            pred = pred[..., :last_frames, :, :]
+        target_m, pred, mm_gt, data_metric_space = process_evaluation_pair(
+            target=target[..., idx * pl:(idx + 1) * pl, :, :], pred_dict={"pred": pred, "obs": new_data})
+        if idx == 0:
+            data = data_metric_space
+        # pred[indeces_bool][..., -n_past_frames:, :, :] keeps the whole segment when it is shorter
+        _, _, best_pred, tail = metrics.best_sample(pred, target_m, tail=min(n_past_frames, pred.shape[2]))
+        final_pred_data.append(best_pred)
+        final_target_data.append(target_m)
+        new_data = tail
+    final_pred_data = torch.cat(final_pred_data, dim=-3)
+    pred = final_pred_data.unsqueeze(1).expand(-1, num_samples, -1, -1, -1)
+    return torch.cat(final_target_data, dim=-3), pred, mm_gt, data
+
+
+def long_term_prediction_best_first50(data, target, extra, get_prediction, process_evaluation_pair=process_evaluation_pair,
+                                      num_samples=50, config=None):
+    """eval_utils.py:69-99: draw num_samples futures once, then continue every one of them with one
+    sample each (`get_prediction(..., num_samples=1)` on B * S rows).  Returns (target, pred, mm_gt, data)."""
+    new_data = data
+    final_pred_data, final_target_data = [], []
+    n_seg, last_frames = _segments(config)
+    pl = config["pred_length"]
+    for idx in range(n_seg):
+        if idx == 0:
+            pred = get_prediction(new_data, num_samples=num_samples, extra=extra)
+        else:
+            batch_size, num_samples, seq_length, num_joints, features = new_data.shape
+            pred = get_prediction(new_data.reshape(batch_size * num_samples, seq_length, num_joints, features),
+                                  num_samples=1, extra=extra)
+            pred = pred.reshape(batch_size, num_samples, pl, num_joints, features)
+        if idx == n_seg - 1 and last_frames is not None:
+            pred = pred[..., :last_frames, :, :]
+        target_m, pred, mm_gt, data_metric_space = process_evaluation_pair(
+            target=target[..., idx * pl:(idx + 1) * pl, :, :], pred_dict={"pred": pred, "obs": new_data})
+        if idx == 0:
+            data = data_metric_space
+        final_pred_data.append(pred)
+        final_target_data.append(target_m)
+        new_data = pred[..., -data.shape[-3]:, :, :]  # cut off the first frames
+    return torch.cat(final_target_data, dim=-3), torch.cat(final_pred_data, dim=-3), mm_gt, data
+
+
+__all__ = ["get_diffusion_latent_codes", "decode_latent_pred", "get_prediction", "process_evaluation_pair",
+           "long_term_prediction_best_every50", "long_term_prediction_best_first50"]

@@ -8,6 +8,10 @@ reduction != 'mean'), reduced in a fixed order (deterministic).
     apd(pred, t0=0, t=-1)             multimodal.py:15-35    mean pairwise L2 over samples
     ade(target, pred, t0, t, reduction)  multimodal.py:44-57  min over samples of mean-frame L2
     fde(target, pred, t0, t, reduction)  multimodal.py:60-73  min over samples of last-frame L2
+    mpjpe(target, pred)               multimodal.py:37-42    min over samples of the mean per-joint L2
+    choose_best_sample / get_best_sample_idx(out, y)  metrics/utils.py:12-30  the sample closest to y
+    best_sample(out, y, tail)         eval_utils.py:59-62    index, distance, trajectory and its last
+                                      `tail` frames in one launch sequence (sd_best_sample)
 
 Up to 64 samples per sequence (the release evaluation draws 50).
 
@@ -138,6 +142,61 @@ def mmfde(target: torch.Tensor, pred: torch.Tensor, mm_gt, t0: int = 0, t: int =
     return _mm(target, pred, mm_gt, t0, t, False)
 
 
+def _best_sample(out, y, tail, want_dist, want_idx, want_best):
+    """One sd_best_sample call: (per_sample (B, S), dist, idx, best, tail), the unwanted ones None."""
+    p, g = _device_tensor(out, "pred"), _device_tensor(y, "target")
+    if p.dim() != 5 or g.dim() != 4 or tuple(g.shape) != (p.shape[0],) + tuple(p.shape[2:]):
+        raise ValueError(f"best sample: pred (B, S, T, J, 3) and target (B, T, J, 3) expected, got "
+                         f"{tuple(p.shape)} and {tuple(g.shape)}")
+    B, S, T, J, C = p.shape
+    tail = 0 if tail is None else int(tail)
+    dev = p.device
+    per = torch.empty(B, S, device=dev, dtype=torch.float32)
+    dist = torch.empty(B, device=dev, dtype=torch.float32) if want_dist else None
+    idx = torch.empty(B, device=dev, dtype=torch.int64) if want_idx else None
+    best = torch.empty(B, T, J, C, device=dev, dtype=torch.float32) if want_best else None
+    # sd_best_sample checks 0 <= tail <= T before it reads the shape of tail_out
+    last = torch.empty(B, tail, J, C, device=dev, dtype=torch.float32) if 0 < tail <= T else None
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    check(_lib.lib().sd_best_sample(p.data_ptr(), g.data_ptr(), B, S, T, J, C, tail, per.data_ptr(), _lib.ptr(dist),
+                                    _lib.ptr(idx), _lib.ptr(best), _lib.ptr(last), stream))
+    return per, dist, idx, best, last
+
+
+def mpjpe(target: torch.Tensor, pred: torch.Tensor, reduction: str = "mean", **kwargs) -> torch.Tensor:
+    """Mean per-joint position error (multimodal.py:37-42): target (batch, seq_length, joints, 3),
+    pred (batch, num_samples, seq_length, joints, 3): min over samples of the mean over frames and
+    joints of the per-joint L2 distance -> (batch,).  As ade / fde, another `reduction` returns the
+    (batch, num_samples) distances before the minimum."""
+    per, dist, _, _, _ = _best_sample(pred, target, None, reduction == "mean", False, False)
+    return dist if reduction == "mean" else per
+
+
+def best_sample(out: torch.Tensor, y: torch.Tensor, tail=None):
+    """The sample closest to the ground truth and what the long-term rollout needs of it
+    (eval_utils.py:59-62), in one launch sequence and without a host synchronisation: out
+    (batch, num_samples, seq_length, joints, 3), y (batch, seq_length, joints, 3) ->
+    (idx int64 (batch,), dist f32 (batch,), best (batch, seq_length, joints, 3),
+    best[:, -tail:] (batch, tail, joints, 3) or None without `tail`).  idx is
+    torch.min(dim).indices of the per-sample distances: the first minimum, the first NaN if any."""
+    _, dist, idx, best, last = _best_sample(out, y, tail, True, True, True)
+    return idx, dist, best, last
+
+
+def get_best_sample_idx(out: torch.Tensor, y: torch.Tensor):
+    """metrics/utils.py:22-30: (out[b, idx[b]] (batch, seq_length, joints, 3), the (batch,
+    num_samples) bool one-hot of idx).  The mask stays on the device."""
+    _, _, idx, best, _ = _best_sample(out, y, None, False, True, True)
+    mask = idx.unsqueeze(1) == torch.arange(out.shape[1], device=idx.device).unsqueeze(0)
+    return best, mask
+
+
+def choose_best_sample(out: torch.Tensor, y: torch.Tensor):
+    """metrics/utils.py:12-20: (the sample closest to y, y)."""
+    _, _, _, best, _ = _best_sample(out, y, None, False, False, True)
+    return best, y
+
+
 def cmd(val_per_frame, val_ref) -> float:
     """Cumulative motion distribution of one class (multimodal.py:10-13): val_per_frame the class's
     mean motion profile M_t (frames - 1 values: array, list or tensor), val_ref its dataset mean
@@ -150,4 +209,5 @@ def cmd(val_per_frame, val_ref) -> float:
     return float(np.sum((T - np.arange(1, T)) * np.abs(v - float(val_ref))))
 
 
-__all__ = ["lat_apd", "apd", "ade", "fde", "mmade", "mmfde", "cmd"]
+__all__ = ["lat_apd", "apd", "ade", "fde", "mmade", "mmfde", "cmd", "mpjpe", "best_sample", "get_best_sample_idx",
+           "choose_best_sample"]

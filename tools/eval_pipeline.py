@@ -6,7 +6,12 @@ T = 10 as the release config).  Prints one JSON line with per-stage times and en
 next to the reference's published end-to-end rate (12,726 AMASS test segments x 50
 futures in ~12 min on an RTX6000 ~ 884 futures/s; data loading included there).
 
-Usage: python tools/eval_pipeline.py [sequences] [T]"""
+With --long-term FACTOR the line also carries the long-term rollout (the reference's
+long_term_prediction_best_every50, eval_utils.py:44-67, through skeletondiffusion_amd.evaluation):
+ceil(FACTOR) segments of 50 futures x 120 frames, the future closest to the ground truth kept and its
+last 30 frames fed back, with per-segment stage times and the total.
+
+Usage: python tools/eval_pipeline.py [sequences] [T] [--long-term FACTOR]"""
 import json
 import sys
 import time
@@ -15,12 +20,18 @@ import torch
 
 sys.path.insert(0, ".")
 from bench import build_config  # noqa: E402
-from skeletondiffusion_amd import metrics, synthetic  # noqa: E402
+from skeletondiffusion_amd import evaluation, metrics, synthetic  # noqa: E402
 from skeletondiffusion_amd.core.network.autoencoder import AutoEncoder  # noqa: E402
 from skeletondiffusion_amd.skeletons import skeleton  # noqa: E402
 
-NSEQ = int(sys.argv[1]) if len(sys.argv) > 1 else 256
-T = int(sys.argv[2]) if len(sys.argv) > 2 else 10
+ARGS = sys.argv[1:]
+LONG_TERM = None
+if "--long-term" in ARGS:
+    _i = ARGS.index("--long-term")
+    LONG_TERM = float(ARGS[_i + 1])
+    del ARGS[_i:_i + 2]
+NSEQ = int(ARGS[0]) if len(ARGS) > 0 else 256
+T = int(ARGS[1]) if len(ARGS) > 1 else 10
 FUT, OBS, PH = 50, 30, 120
 cuda = torch.device("cuda:0")
 d, _, _ = build_config("amass21", cuda, T=T, batch=1, futures=FUT)
@@ -57,14 +68,54 @@ def run():
     return st, float(apd.mean()), float(ade.mean()), float(fde.mean())
 
 
+def run_long_term(factor):
+    """best_every50 on the same setup: (per-segment stage ms, device ms of the rollout, mpjpe of the
+    returned trajectory against the long target)."""
+    frames = int(factor * PH)
+    long_target = (torch.from_numpy(synthetic.normal((NSEQ, frames, J, 3), seed=53)) * 0.3).to(cuda)
+    marks = []
+
+    def predict(past, **kwargs):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record()
+        lat, z_past = evaluation.get_diffusion_latent_codes(past, (ae, d), num_samples=FUT, sampler_kwargs={"seed": 7})
+        ev[1].record()
+        pred = evaluation.decode_latent_pred(past, lat, z_past, (ae, d), num_samples=FUT, pred_length=PH)
+        ev[2].record()
+        marks.append(ev)
+        return pred
+
+    _, pred, _, _ = evaluation.long_term_prediction_best_every50(
+        obs, long_target, None, predict, num_samples=FUT, config={"long_term_factor": factor, "pred_length": PH})
+    end = torch.cuda.Event(enable_timing=True)
+    end.record()
+    torch.cuda.synchronize()
+    segs = []
+    for k, ev in enumerate(marks):  # the selection runs from a segment's decode to the next segment's start
+        nxt = marks[k + 1][0] if k + 1 < len(marks) else end
+        segs.append({"encode_sample": ev[0].elapsed_time(ev[1]), "decode": ev[1].elapsed_time(ev[2]),
+                     "select": ev[2].elapsed_time(nxt)})
+    mp = metrics.mpjpe(long_target, pred[:, :1])
+    return segs, marks[0][0].elapsed_time(end), float(mp.mean()), frames
+
+
 run()  # warm-up: plans, graphs, workspaces
 t0 = time.perf_counter()
 st, apd, ade, fde = run()
 wall = time.perf_counter() - t0
 rows = NSEQ * FUT
+extra = {}
+if LONG_TERM is not None:
+    run_long_term(LONG_TERM)  # warm-up: the last segment's shapes
+    t0 = time.perf_counter()
+    segs, dev_ms, mp, frames = run_long_term(LONG_TERM)
+    extra = {"long_term": {"factor": LONG_TERM, "segments": len(segs), "frames": frames, "segment_stage_ms": segs,
+                           "device_ms": dev_ms, "wall_ms": (time.perf_counter() - t0) * 1e3,
+                           "futures_per_s": rows * len(segs) / (dev_ms * 1e-3), "mpjpe_best": mp}}
 print(json.dumps({"metric": "end-to-end evaluated futures/s (encode + sample + decode + APD/ADE/FDE)",
                   "value": rows / wall, "unit": "futures/s", "sequences": NSEQ, "futures": FUT, "J": J, "T": T,
                   "obs_frames": OBS, "pred_frames": PH, "wall_ms": wall * 1e3, "stage_ms": st,
                   "apd": apd, "ade": ade, "fde": fde, "data": "synthetic weights and motions",
                   "reference_published": {"value": 884, "unit": "futures/s end-to-end",
-                                          "hardware": "NVIDIA RTX6000", "source": "BASELINE.md (README.md:223)"}}))
+                                          "hardware": "NVIDIA RTX6000", "source": "BASELINE.md (README.md:223)"},
+                  **extra}))
