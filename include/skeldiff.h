@@ -273,6 +273,47 @@ int sd_best_sample(const float* pred, const float* target, int64_t nseq, int32_t
                    int32_t joints, int32_t coords, int32_t tail_frames, float* per_sample, float* min_out,
                    int64_t* idx_out, float* best_out, float* tail_out, void* stream);
 
+/* Body-realism, limb-angle and motion-profile metrics (reference src/metrics/body_realism.py:109-199
+ * limb_stretching_normed_rmse / _mean and limb_jitter_normed_rmse / _mean, src/metrics/multimodal.py:76-102
+ * mae, src/metrics/cmd.py:10-12 motion_for_cmd) from one read of pred (nseq, samples, frames, joints, 3);
+ * target (nseq, target_frames, joints, 3); f32, dense, 4-byte aligned (16-byte loads where the addresses
+ * allow).  limbseq (nlimbs, 2) joint indices and angle_pairs (npairs, 2) limb indices (the consecutive
+ * pairs of the reference's limb_angles_idx chains) are HOST int32 arrays, checked and passed to the
+ * kernels by value.  All arithmetic on limb lengths and angles is f64, every sum has a fixed order that
+ * depends on (frame, limb / pair / joint) only; results are f32.  A ground-truth limb of zero mean length
+ * divides by zero, as in the reference.
+ * sd_realism_target: the ground-truth pass.
+ *   gt_len_mean (nseq, nlimbs) f64   mean over the target's frames of each limb's length; required
+ *   gt_cos, gt_ang (nseq, frames, npairs) f64   per frame and pair the cosine between the two limbs
+ *                               (limb vectors along the sorted limbseq, denominator clamped at 1e-7) and
+ *                               acos of its clamp to [-1, 1]; NULL unless angles are wanted (gt_ang needs gt_cos)
+ * sd_realism: the pass over the predictions, then the per-sequence reductions.  Every output may be NULL
+ * and is then not computed; q = 0..5 is srmse_std, srmse_var, jrmse_std, jrmse_var, smean, jmean.
+ *   none_out (6, nseq, samples, nlimbs)     reduction 'none' of the six quantities
+ *   persample_out (6, nseq, samples)        their means over the limbs ('persample')
+ *   limb_scratch (6, nseq, samples, nlimbs) f64, workspace of mean_out
+ *   mean_out (6, nseq)                      their means over samples and limbs ('mean')
+ *   angle_persample, cossim_persample (nseq, samples)  mean over frames and pairs of |acos - acos_gt| and
+ *                               of |cos - cos_gt|, both times 180 / pi (mae with if_return_cossim False / True)
+ *   angle_min, cossim_min (nseq)            their minima over the samples (NaN if any); each needs its persample
+ *   motion_scratch (nseq, samples, frames - 1)  mean over joints of ||pred_t - pred_{t-1}||, workspace of
+ *   motion_out (nseq, frames - 1)           its mean over the samples (motion_for_cmd); frames == 1: untouched
+ * The float32 jitter quantities of frames == 1 are NaN (0 / 0), as the reference's.  target_frames is the
+ * frame count gt_len_mean was taken over (limb_stretching_normed_mean with obs_as_target); angle outputs
+ * need target_frames == frames.  1 <= samples, joints, nlimbs <= 64, 0 <= npairs <= 64, frames >= 1, every
+ * limbseq entry in [0, joints), every angle_pairs entry in [0, nlimbs) (SD_E_INVALID names the argument,
+ * before any device call); nseq == 0 launches nothing.
+ * sd_realism_frame_tile: the number of frames the prediction pass stages at a time for `joints` joints. */
+int sd_realism_target(const float* target, int64_t nseq, int32_t frames, int32_t joints, const int32_t* limbseq,
+                      int32_t nlimbs, const int32_t* angle_pairs, int32_t npairs, double* gt_len_mean, double* gt_cos,
+                      double* gt_ang, void* stream);
+int sd_realism(const float* pred, int64_t nseq, int32_t samples, int32_t frames, int32_t joints, const int32_t* limbseq,
+               int32_t nlimbs, const int32_t* angle_pairs, int32_t npairs, const double* gt_len_mean,
+               const double* gt_cos, const double* gt_ang, int32_t target_frames, float* none_out, float* persample_out,
+               double* limb_scratch, float* mean_out, float* angle_persample, float* cossim_persample, float* angle_min,
+               float* cossim_min, float* motion_scratch, float* motion_out, void* stream);
+int32_t sd_realism_frame_tile(int32_t joints);
+
 /* Test hooks: one kernel on caller buffers, for the per-kernel numerics tests.
  * sd_test_graph_linear: out(B,J,N) = act(FiLM(ghat @ (s_j W[type j] [x1_j | x2_j] + bias[type j]))) + res,
  *   W (types,N,K1+K2), bias (types,N) or NULL, ghat (J,J), film (2N) or NULL, res (B,J,N) or NULL,

@@ -41,6 +41,7 @@ EXPORTED = (
     "sd_l1norm_rows_backward", "sd_rmsnorm_workspace_bytes", "sd_rmsnorm_forward", "sd_rmsnorm_backward",
     "sd_mahalanobis_loss_forward", "sd_mahalanobis_loss_backward", "sd_best_of_k", "sd_best_of_k_backward",
     "sd_pose_loss", "sd_test_set_split_route", "sd_chain_start", "sd_chain_tile_unit", "sd_best_sample",
+    "sd_realism_target", "sd_realism", "sd_realism_frame_tile",
 )
 
 # sd_plan_set_option keys (include/skeldiff.h)
@@ -160,6 +161,11 @@ def _declare(lib: ctypes.CDLL) -> None:
         "sd_best_of_k_backward": (ctypes.c_int, [vp, vp, i64, i32, vp, vp]),
         "sd_pose_loss": (ctypes.c_int, [vp, vp, i64, i32, i32, i32, i32, i32, vp, vp]),
         "sd_best_sample": (ctypes.c_int, [vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+        "sd_realism_target": (ctypes.c_int, [vp, i64, i32, i32, ctypes.POINTER(i32), i32, ctypes.POINTER(i32), i32, vp,
+                                             vp, vp, vp]),
+        "sd_realism": (ctypes.c_int, [vp, i64, i32, i32, i32, ctypes.POINTER(i32), i32, ctypes.POINTER(i32), i32, vp, vp,
+                                      vp, i32] + [vp] * 10 + [vp]),
+        "sd_realism_frame_tile": (i32, [i32]),
         "sd_profile_step": (ctypes.c_int, [vp, vp, vp, i64, i32, i64, vp, sz, i32, ctypes.POINTER(ctypes.c_float),
                                            ctypes.POINTER(ctypes.c_int32), vp]),
     }

@@ -7,6 +7,7 @@ and the long-term rollouts (src/eval_utils.py:44-99), with the reference's signa
     long_term_prediction_best_every50(...)   draw S futures, keep the one closest to the ground truth,
                                              feed its last observed-length frames back, repeat
     long_term_prediction_best_first50(...)   draw S futures once, then continue each of them
+    get_stats_funcs(stats_mode, skeleton_key)   the metric dict of an evaluation loop (src/config_metrics.py:18-53)
 
 `model` is the (autoencoder, diffusion) pair of `prepare_model`.  Every stage is a HIP kernel sequence
 (sd_gru_encode, sd_sample_loop, sd_gru_decode, sd_best_sample); nothing here copies to the host or
@@ -15,10 +16,11 @@ synchronises, so the segments of a rollout queue back to back on the stream.
 from __future__ import annotations
 
 import math
+from functools import partial
 
 import torch
 
-from . import metrics
+from . import metrics, skeletons
 
 
 def get_diffusion_latent_codes(obs, model, num_samples=50, diffusion_conditioning=True, sampler_kwargs=None, **kwargs):
@@ -131,5 +133,39 @@ def long_term_prediction_best_first50(data, target, extra, get_prediction, proce
     return torch.cat(final_target_data, dim=-3), torch.cat(final_pred_data, dim=-3), mm_gt, data
 
 
+def _times_100(fn):
+    """config_metrics.py:23-27: the body-realism values are reported in per cent of the limb length."""
+    def scaled(*args, **kwargs):
+        return fn(*args, **kwargs) * 100
+    return scaled
+
+
+def get_stats_funcs(stats_mode, skeleton_key, **kwargs):
+    """config_metrics.py:18-53: name -> metric function of an evaluation loop, every one on the device
+    (`skeletondiffusion_amd.metrics`), for stats_mode 'deterministic', 'probabilistic_orig' or
+    'probabilistic' (the release setting).  `skeleton_key` names the limb tables
+    (`skeletons.limbseq / limb_angles_idx`: 'h36m16', 'amass21', 'freeman17', 'mano51'); the hip is not a
+    node (the reference asserts `not if_consider_hip`).  Each function is called as the reference's:
+    `fn(pred=..., target=..., mm_gt=..., ...)`."""
+    assert not kwargs.get("if_consider_hip", False)
+    limbseq, limb_angles_idx = skeletons.limbseq(skeleton_key), skeletons.limb_angles_idx(skeleton_key)
+    realism = {
+        "StretchMean": partial(_times_100(metrics.limb_stretching_normed_mean), limbseq=limbseq),
+        "JitterMean": partial(_times_100(metrics.limb_jitter_normed_mean), limbseq=limbseq),
+        "StretchRMSE": partial(_times_100(metrics.limb_stretching_normed_rmse), limbseq=limbseq),
+        "JitterRMSE": partial(_times_100(metrics.limb_jitter_normed_rmse), limbseq=limbseq),
+    }
+    mae = partial(metrics.mae, limbseq=limbseq, limb_angles_idx=limb_angles_idx)
+    mode = stats_mode.lower()
+    if "deterministic" in mode:
+        return {"ADE": metrics.ade, "FDE": metrics.fde, "MAE": mae, "APD": metrics.apd, **realism}
+    if mode == "probabilistic_orig":
+        return {"APD": metrics.apd, "ADE": metrics.ade, "FDE": metrics.fde, "MMADE": metrics.mmade, "MMFDE": metrics.mmfde}
+    if mode == "probabilistic":
+        return {"ADE": metrics.ade, "FDE": metrics.fde, "MAE": mae, "MMADE": metrics.mmade, "MMFDE": metrics.mmfde,
+                "APD": metrics.apd, **realism}
+    raise NotImplementedError(f"stats_mode not implemented: {stats_mode}")
+
+
 __all__ = ["get_diffusion_latent_codes", "decode_latent_pred", "get_prediction", "process_evaluation_pair",
-           "long_term_prediction_best_every50", "long_term_prediction_best_first50"]
+           "long_term_prediction_best_every50", "long_term_prediction_best_first50", "get_stats_funcs"]

@@ -13,12 +13,22 @@ reduction != 'mean'), reduced in a fixed order (deterministic).
     best_sample(out, y, tail)         eval_utils.py:59-62    index, distance, trajectory and its last
                                       `tail` frames in one launch sequence (sd_best_sample)
 
-Up to 64 samples per sequence (the release evaluation draws 50).
+    limb_stretching_normed_rmse / _mean, limb_jitter_normed_rmse / _mean(pred, target, limbseq, ...)
+                                      body_realism.py:109-199  limb stretching and jitter over the gt limb length
+    mae(target, pred, limbseq, limb_angles_idx, t0, t, if_return_cossim)  multimodal.py:76-102  limb-angle error
+    motion_for_cmd(pred)              cmd.py:10-12           the CMD's motion profile (B, T - 1)
+    realism(pred, target, limbseq, limb_angles_idx)  all of the four lines above from one read of pred
+                                      (sd_realism_target + sd_realism; float64 inside)
+
+Up to 64 samples per sequence (the release evaluation draws 50); up to 64 joints, limbs and angle pairs.
 
 cmd(val_per_frame, val_ref) (multimodal.py:10-13) is the one host-side function here: the CMD score of
 a class's mean motion profile, a sum over at most a few hundred frame steps.
 """
 from __future__ import annotations
+
+import collections
+import ctypes
 
 import torch
 
@@ -209,5 +219,148 @@ def cmd(val_per_frame, val_ref) -> float:
     return float(np.sum((T - np.arange(1, T)) * np.abs(v - float(val_ref))))
 
 
+# ---- body realism, limb angles, motion profile (sd_realism_target + sd_realism) --------
+_QUANTITIES = ("srmse_std", "srmse_var", "jrmse_std", "jrmse_var", "smean", "jmean")
+_REDUCTIONS = ("mean", "persample", "none")
+Realism = collections.namedtuple(
+    "Realism", [f"{q}_{r}" for q in _QUANTITIES for r in _REDUCTIONS] +
+    ["mae", "mae_persample", "mae_cossim", "mae_cossim_persample", "motion"])
+Realism.__doc__ = """What `realism` returns: `{quantity}_{reduction}` for srmse / jrmse (`std`, `var`), smean and jmean
+(limb_stretching_normed_rmse, limb_jitter_normed_rmse, limb_stretching_normed_mean, limb_jitter_normed_mean)
+with reduction mean (B,), persample (B, S) and none (B, S, L); mae / mae_cossim (B,) and their (B, S)
+values before the minimum (None without limb_angles_idx); motion (B, T - 1)."""
+
+
+def _int_table(rows, name: str):
+    """A (n, 2) integer table (list, array or tensor) as a host int32 ctypes array and n."""
+    rows = rows.tolist() if hasattr(rows, "tolist") else list(rows)
+    flat = []
+    for r in rows:
+        if len(r) != 2:
+            raise ValueError(f"{name}: rows of two indices expected, got {r}")
+        flat += [int(r[0]), int(r[1])]
+    return (ctypes.c_int32 * max(len(flat), 1))(*flat), len(rows)
+
+
+def _angle_pairs(limb_angles_idx):
+    """multimodal.py:87: the consecutive limb pairs of every kinematic chain."""
+    return [[kin[i], kin[i + 1]] for kin in limb_angles_idx for i in range(len(kin) - 1)]
+
+
+def _realism(pred, target, limbseq, limb_angles_idx, want, obs_as_target=False):
+    """One sd_realism_target + sd_realism call computing the groups in `want` (a subset of 'none',
+    'persample', 'mean', 'angle', 'cossim', 'motion'); -> dict of the raw output arrays."""
+    p, g = _device_tensor(pred, "pred"), _device_tensor(target, "target")
+    if p.dim() != 5 or g.dim() != 4 or p.shape[4] != 3 or (g.shape[0],) + tuple(g.shape[2:]) != (p.shape[0],) + tuple(p.shape[3:]):
+        raise ValueError(f"realism: pred (B, S, T, J, 3) and target (B, T, J, 3) expected, got {tuple(p.shape)} and "
+                         f"{tuple(g.shape)}")
+    B, S, T, J, _ = p.shape
+    Tt = g.shape[1]
+    if Tt != T and not obs_as_target:  # body_realism.py:115
+        raise ValueError(f"realism: target has {Tt} frames, pred {T} (only limb_stretching_normed_mean takes another "
+                         "count, with obs_as_target)")
+    angles = "angle" in want or "cossim" in want
+    limbs, L = _int_table(limbseq, "limbseq")
+    pairs, P = _int_table(_angle_pairs(limb_angles_idx) if angles else [], "limb_angles_idx")
+    dev = p.device
+    f32 = dict(device=dev, dtype=torch.float32)
+    f64 = dict(device=dev, dtype=torch.float64)
+    gt_len = torch.empty(B, L, **f64)
+    gt_cos = torch.empty(B, Tt, P, **f64) if angles else None
+    gt_ang = torch.empty(B, Tt, P, **f64) if "angle" in want else None
+    o = {
+        "none": torch.empty(6, B, S, L, **f32) if "none" in want else None,
+        "persample": torch.empty(6, B, S, **f32) if "persample" in want else None,
+        "scratch": torch.empty(6, B, S, L, **f64) if "mean" in want else None,
+        "mean": torch.empty(6, B, **f32) if "mean" in want else None,
+        "angle_ps": torch.empty(B, S, **f32) if "angle" in want else None,
+        "cossim_ps": torch.empty(B, S, **f32) if "cossim" in want else None,
+        "angle": torch.empty(B, **f32) if "angle" in want else None,
+        "cossim": torch.empty(B, **f32) if "cossim" in want else None,
+        "motion_scratch": torch.empty(B, S, T - 1, **f32) if "motion" in want else None,
+        "motion": torch.empty(B, T - 1, **f32) if "motion" in want else None,
+    }
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    L_ = _lib.lib()
+    check(L_.sd_realism_target(g.data_ptr(), B, Tt, J, limbs, L, pairs, P, gt_len.data_ptr(), _lib.ptr(gt_cos),
+                               _lib.ptr(gt_ang), stream))
+    check(L_.sd_realism(p.data_ptr(), B, S, T, J, limbs, L, pairs, P, gt_len.data_ptr(), _lib.ptr(gt_cos),
+                        _lib.ptr(gt_ang), Tt, *(_lib.ptr(o[k]) for k in ("none", "persample", "scratch", "mean", "angle_ps",
+                                                                        "cossim_ps", "angle", "cossim", "motion_scratch",
+                                                                        "motion")), stream))
+    return o
+
+
+def realism(pred: torch.Tensor, target: torch.Tensor, limbseq, limb_angles_idx=None) -> Realism:
+    """Every body-realism quantity, the limb-angle errors and the motion profile from one launch
+    sequence and one read of pred (B, S, T, J, 3); target (B, T, J, 3); limbseq (L, 2) joint indices,
+    limb_angles_idx the kinematic chains of limb indices (`skeletons.limbseq / limb_angles_idx`).
+    Without limb_angles_idx the angle fields are None and no acos is evaluated.  -> `Realism`."""
+    want = {"none", "persample", "mean", "motion"} | ({"angle", "cossim"} if limb_angles_idx is not None else set())
+    o = _realism(pred, target, limbseq, limb_angles_idx, want)
+    vals = [o[r][q] for q in range(6) for r in _REDUCTIONS]
+    return Realism(*vals, o["angle"], o["angle_ps"], o["cossim"], o["cossim_ps"], o["motion"])
+
+
+def _limb_metric(q, pred, target, limbseq, reduction, obs_as_target=False):
+    r = reduction if reduction in ("mean", "persample") else "none"
+    return _realism(pred, target, limbseq, None, {r}, obs_as_target)[r][q]
+
+
+def _mode(mode):
+    assert mode in ("std", "var"), f"Mode {mode} not supported"  # body_realism.py:110
+    return 0 if mode == "std" else 1
+
+
+def limb_stretching_normed_rmse(pred, target, limbseq, mode="std", reduction="mean", **kwargs):
+    """body_realism.py:109-129: per limb sqrt (mode 'std') or not ('var') of the mean over frames of
+    (length - gt mean length)^2, over the gt mean length; reduction 'mean' (B,), 'persample' (B, S), else (B, S, L)."""
+    return _limb_metric(_mode(mode), pred, target, limbseq, reduction)
+
+
+def limb_jitter_normed_rmse(pred, target, limbseq, mode="std", reduction="mean", **kwargs):
+    """body_realism.py:150-176: as limb_stretching_normed_rmse on the frame-to-frame change of the limb lengths."""
+    return _limb_metric(2 + _mode(mode), pred, target, limbseq, reduction)
+
+
+def limb_stretching_normed_mean(pred, target, limbseq, reduction="mean", obs_as_target=False, **kwargs):
+    """body_realism.py:131-147: |mean limb length - gt mean length| / gt mean length; with obs_as_target
+    the target may have another frame count (the observation)."""
+    return _limb_metric(4, pred, target, limbseq, reduction, obs_as_target)
+
+
+def limb_jitter_normed_mean(pred, target, limbseq, reduction="mean", **kwargs):
+    """body_realism.py:178-199: mean |frame-to-frame change of the limb length| / gt mean length."""
+    return _limb_metric(5, pred, target, limbseq, reduction)
+
+
+def mae(target, pred, limbseq, limb_angles_idx, t0=0, t=-1, if_return_cossim=False, reduction="mean", **kwargs):
+    """Limb-angle error in degrees (multimodal.py:76-102): min over samples of the mean over frames and
+    angle pairs of |acos(cos_pred) - acos(cos_gt)| (of |cos_pred - cos_gt| with if_return_cossim), times
+    180 / pi.  As ade / mpjpe, another `reduction` returns the (batch, num_samples) values before the minimum."""
+    pred, target = _time_slice(pred, t0, t, 2), _time_slice(target, t0, t, 1)
+    k = "cossim" if if_return_cossim else "angle"
+    o = _realism(pred, target, limbseq, limb_angles_idx, {k})
+    return o[k] if reduction == "mean" else o[k + "_ps"]
+
+
+def motion_for_cmd(pred: torch.Tensor) -> torch.Tensor:
+    """cmd.py:10-12: pred (B, S, T, J, 3) -> (B, T - 1), the mean over samples and joints of the
+    joints' frame-to-frame displacement."""
+    p = _device_tensor(pred, "pred")
+    if p.dim() != 5 or p.shape[4] != 3:
+        raise ValueError(f"motion_for_cmd: pred (B, S, T, J, 3) expected, got {tuple(p.shape)}")
+    B, S, T = p.shape[:3]
+    limbs, _ = _int_table([[0, 0]], "limbseq")  # no limb output is asked for; the argument check wants one limb
+    gt_len = torch.ones(B, 1, device=p.device, dtype=torch.float64)
+    scratch = torch.empty(B, S, T - 1, device=p.device, dtype=torch.float32)
+    motion = torch.empty(B, T - 1, device=p.device, dtype=torch.float32)
+    stream = torch.cuda.current_stream(p.device).cuda_stream
+    check(_lib.lib().sd_realism(p.data_ptr(), B, S, T, p.shape[3], limbs, 1, None, 0, gt_len.data_ptr(), None, None, T,
+                                *([None] * 8), scratch.data_ptr(), motion.data_ptr(), stream))
+    return motion
+
+
 __all__ = ["lat_apd", "apd", "ade", "fde", "mmade", "mmfde", "cmd", "mpjpe", "best_sample", "get_best_sample_idx",
-           "choose_best_sample"]
+           "choose_best_sample", "limb_stretching_normed_rmse", "limb_stretching_normed_mean", "limb_jitter_normed_rmse",
+           "limb_jitter_normed_mean", "mae", "motion_for_cmd", "realism", "Realism"]

@@ -82,3 +82,42 @@ def skeleton(key: str):
     uniq = list(dict.fromkeys(stripped))
     types = np.array([uniq.index(s) for s in stripped], dtype=np.int64)
     return nodes, node_limbs, adj, types
+
+
+# ---- limb tables of the evaluation metrics ------------------------------------------------------------
+# The reference's skeleton.get_limbseq() and skeleton.limb_angles_idx (if_consider_hip=False), as the
+# body-realism metrics and the limb-angle MAE take them (src/config_metrics.py:18-21), in the
+# reference's order: the angle chains index into limbseq.  tests/test_realism_host.py pins them to
+# tests/golden/realism.npz.
+def _mano_hand_limbs_by_depth(wrist: int, first: int) -> List[Tuple[int, int]]:
+    """One hand's limbs as the reference lists them: the five wrist-to-finger limbs, then each finger's two."""
+    bases = [first + 3 * f for f in range(5)]
+    return [(wrist, b) for b in bases] + [l for b in bases for l in ((b, b + 1), (b + 1, b + 2))]
+
+
+# kinematic chains of limb indices; mae compares the angle between each consecutive pair of a chain
+_LIMB_ANGLE_CHAINS: Dict[str, List[List[int]]] = {
+    "h36m16": [[3, 4], [0, 2, 7, 8, 9], [1, 7, 10, 12, 13], [7, 11, 14, 15]],
+    "amass21": [[0, 2, 3, 4, 5, 6], [0, 3], [4, 7, 8, 9, 10], [4, 11, 12, 13, 14], [0, 15, 16, 17], [18, 19, 20]],
+    "freeman17": [[0, 1, 7, 9], [0, 4, 6], [1, 8, 10], [3, 5], [2, 11, 13, 15], [1, 12, 14, 16]],
+}
+_LIMB_ANGLE_CHAINS["mano51"] = _LIMB_ANGLE_CHAINS["amass21"]  # the body's chains; the fingers have none
+
+
+def limbseq(key: str) -> List[List[int]]:
+    """The (L, 2) joint-index pairs of a skeleton's limbs (hip excluded), in the reference's order."""
+    if key not in _LIMB_ANGLE_CHAINS:
+        raise KeyError(f"no limb tables for skeleton {key!r} (have {sorted(_LIMB_ANGLE_CHAINS)})")
+    if key == "mano51":  # the body's limbs, then per hand wrist-to-finger limbs before the finger segments
+        limbs = skeleton("amass21")[1] + _mano_hand_limbs_by_depth(19, 21) + _mano_hand_limbs_by_depth(20, 36)
+    else:
+        limbs = skeleton(key)[1]
+    return [[int(a), int(b)] for a, b in limbs]
+
+
+def limb_angles_idx(key: str) -> List[List[int]]:
+    """The kinematic chains of limb indices (into `limbseq(key)`) whose consecutive limbs form the
+    angles of the limb-angle MAE (multimodal.py:76-102)."""
+    if key not in _LIMB_ANGLE_CHAINS:
+        raise KeyError(f"no limb tables for skeleton {key!r} (have {sorted(_LIMB_ANGLE_CHAINS)})")
+    return [list(c) for c in _LIMB_ANGLE_CHAINS[key]]

@@ -11,7 +11,10 @@ long_term_prediction_best_every50, eval_utils.py:44-67, through skeletondiffusio
 ceil(FACTOR) segments of 50 futures x 120 frames, the future closest to the ground truth kept and its
 last 30 frames fed back, with per-segment stage times and the total.
 
-Usage: python tools/eval_pipeline.py [sequences] [T] [--long-term FACTOR]"""
+With --realism the fused body-realism / limb-angle / motion-profile call (metrics.realism)
+runs after the existing metrics on the same decoded futures, and its milliseconds are reported.
+
+Usage: python tools/eval_pipeline.py [sequences] [T] [--long-term FACTOR] [--realism]"""
 import json
 import sys
 import time
@@ -20,11 +23,14 @@ import torch
 
 sys.path.insert(0, ".")
 from bench import build_config  # noqa: E402
-from skeletondiffusion_amd import evaluation, metrics, synthetic  # noqa: E402
+from skeletondiffusion_amd import evaluation, metrics, skeletons, synthetic  # noqa: E402
 from skeletondiffusion_amd.core.network.autoencoder import AutoEncoder  # noqa: E402
 from skeletondiffusion_amd.skeletons import skeleton  # noqa: E402
 
 ARGS = sys.argv[1:]
+REALISM = "--realism" in ARGS
+if REALISM:
+    ARGS.remove("--realism")
 LONG_TERM = None
 if "--long-term" in ARGS:
     _i = ARGS.index("--long-term")
@@ -49,7 +55,7 @@ target = (torch.from_numpy(synthetic.normal((NSEQ, PH, J, 3), seed=52)) * 0.3).t
 
 def run():
     st = {}
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
     ev[0].record()
     z_past = ae.get_past_embedding(obs)
     ev[1].record()
@@ -62,9 +68,18 @@ def run():
     ade = metrics.ade(target, p)
     fde = metrics.fde(target, p)
     ev[4].record()
+    real = metrics.realism(p, target, skeletons.limbseq("amass21"), skeletons.limb_angles_idx("amass21")) if REALISM else None
+    ev[5].record()
     torch.cuda.synchronize()
     for k, (a, b) in zip(("encode", "sample", "decode", "metrics"), zip(ev, ev[1:])):
         st[k] = a.elapsed_time(b)
+    if REALISM:
+        st["realism"] = ev[4].elapsed_time(ev[5])
+        st["realism_values"] = {"MAE": float(real.mae.mean()), "StretchMean": 100 * float(real.smean_mean.mean()),
+                                "JitterMean": 100 * float(real.jmean_mean.mean()),
+                                "StretchRMSE": 100 * float(real.srmse_std_mean.mean()),
+                                "JitterRMSE": 100 * float(real.jrmse_std_mean.mean()),
+                                "motion_mean": float(real.motion.mean())}
     return st, float(apd.mean()), float(ade.mean()), float(fde.mean())
 
 
