@@ -314,6 +314,40 @@ int sd_realism(const float* pred, int64_t nseq, int32_t samples, int32_t frames,
                float* cossim_min, float* motion_scratch, float* motion_out, void* stream);
 int32_t sd_realism_frame_tile(int32_t joints);
 
+/* FID on the device (reference src/metrics/fid.py:91-129 MetricStorerFID, src/metrics/fid_classifier.py:38-53
+ * ClassifierForFID.get_fid_features).  The classifier is nn.GRU(input_size, 128, 2) over the frames followed
+ * by tanh(linear1(h_last)); every pointer of the desc is a DEVICE f32 array in torch's layout: weight_ih_l0
+ * (3 * 128, input_size), the other GRU weights (3 * 128, 128), the GRU biases (3 * 128), gate order r, z, n,
+ * linear1_weight (feat_size, 128), linear1_bias (feat_size).
+ * sd_fid_features (fid_classifier.py:43-53 and the reshape / permute copies of fid.py:111-120): one launch runs
+ *   both layers over all frames for tiles of 32 rows and writes feats (rows, feat_size).
+ *   motion (rows, frames, input_size) f32, dense: pred (B, S, T, J, 3) and target (B, T, J, 3) as they stand
+ *   h0 (2, rows, 128) the initial hidden states, NULL = zeros
+ *   workspace   sd_fid_workspace_bytes(desc, rows) bytes (the weights in matrix-instruction order, rewritten
+ *               by every call: the desc's arrays may change between calls)
+ *   All products are exact f32 (v_mfma_f32_32x32x2_f32); every sum has a fixed order that does not depend on
+ *   the row's place in its tile, so a row's features are bitwise independent of the batch.
+ *   hidden_size == 128, 1 <= feat_size <= 32, 1 <= input_size <= 64, frames >= 1, rows >= 0, workspace_bytes
+ *   large enough (SD_E_INVALID names the argument, before any device call); rows == 0 launches nothing.
+ *   sd_fid_workspace_bytes returns 0 for an invalid desc.
+ * sd_fid_stats_update (fid.py:7-11 _calculate_activation_statistics, streamed): adds the batch's
+ *   (count, sum x, sum x x^T) to state (1 + feat + feat * feat) f64: state[0] the row count, state[1 + a] the
+ *   sums, state[1 + feat + a * feat + b] the products.  float64, rows in chunks of 256 (a chunk in row order,
+ *   then the chunks in order), no atomics: the same calls give the same bits.  workspace:
+ *   sd_fid_stats_workspace_bytes(rows, feat) bytes.  1 <= feat <= 32; rows == 0 launches nothing. */
+typedef struct sd_fid_classifier_desc {
+    int32_t input_size, hidden_size, feat_size; /* 48, 128, 30 in the release */
+    const float *weight_ih_l0, *weight_hh_l0, *bias_ih_l0, *bias_hh_l0;
+    const float *weight_ih_l1, *weight_hh_l1, *bias_ih_l1, *bias_hh_l1;
+    const float *linear1_weight, *linear1_bias;
+} sd_fid_classifier_desc;
+size_t sd_fid_workspace_bytes(const sd_fid_classifier_desc* desc, int64_t rows);
+int sd_fid_features(const sd_fid_classifier_desc* desc, const float* motion, int64_t rows, int32_t frames,
+                    const float* h0, float* feats, void* workspace, size_t workspace_bytes, void* stream);
+size_t sd_fid_stats_workspace_bytes(int64_t rows, int32_t feat);
+int sd_fid_stats_update(const float* feats, int64_t rows, int32_t feat, double* state, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* Test hooks: one kernel on caller buffers, for the per-kernel numerics tests.
  * sd_test_graph_linear: out(B,J,N) = act(FiLM(ghat @ (s_j W[type j] [x1_j | x2_j] + bias[type j]))) + res,
  *   W (types,N,K1+K2), bias (types,N) or NULL, ghat (J,J), film (2N) or NULL, res (B,J,N) or NULL,

@@ -42,6 +42,7 @@ EXPORTED = (
     "sd_mahalanobis_loss_forward", "sd_mahalanobis_loss_backward", "sd_best_of_k", "sd_best_of_k_backward",
     "sd_pose_loss", "sd_test_set_split_route", "sd_chain_start", "sd_chain_tile_unit", "sd_best_sample",
     "sd_realism_target", "sd_realism", "sd_realism_frame_tile",
+    "sd_fid_workspace_bytes", "sd_fid_features", "sd_fid_stats_workspace_bytes", "sd_fid_stats_update",
 )
 
 # sd_plan_set_option keys (include/skeldiff.h)
@@ -85,6 +86,14 @@ class SDGruDecoderDesc(ctypes.Structure):
                [("node_types", ctypes.POINTER(ctypes.c_int64))] + \
                [(n, ctypes.c_void_p) for n in ("init_G", "init_weight", "init_bias", "G", "G_add", "weight_ih",
                                                "weight_hh", "bias_ih", "bias_hh", "fc_G", "fc_weight", "fc_bias")]
+
+
+class SDFidClassifierDesc(ctypes.Structure):
+    """mirrors struct sd_fid_classifier_desc (include/skeldiff.h)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("input_size", "hidden_size", "feat_size")] + \
+               [(n, ctypes.c_void_p) for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0",
+                                               "weight_ih_l1", "weight_hh_l1", "bias_ih_l1", "bias_hh_l1",
+                                               "linear1_weight", "linear1_bias")]
 
 
 class SkelDiffError(RuntimeError):
@@ -166,6 +175,10 @@ def _declare(lib: ctypes.CDLL) -> None:
         "sd_realism": (ctypes.c_int, [vp, i64, i32, i32, i32, ctypes.POINTER(i32), i32, ctypes.POINTER(i32), i32, vp, vp,
                                       vp, i32] + [vp] * 10 + [vp]),
         "sd_realism_frame_tile": (i32, [i32]),
+        "sd_fid_workspace_bytes": (sz, [ctypes.POINTER(SDFidClassifierDesc), i64]),
+        "sd_fid_features": (ctypes.c_int, [ctypes.POINTER(SDFidClassifierDesc), vp, i64, i32, vp, vp, vp, sz, vp]),
+        "sd_fid_stats_workspace_bytes": (sz, [i64, i32]),
+        "sd_fid_stats_update": (ctypes.c_int, [vp, i64, i32, vp, vp, sz, vp]),
         "sd_profile_step": (ctypes.c_int, [vp, vp, vp, i64, i32, i64, vp, sz, i32, ctypes.POINTER(ctypes.c_float),
                                            ctypes.POINTER(ctypes.c_int32), vp]),
     }

@@ -19,7 +19,7 @@ from typing import Any, Dict, Optional
 import torch
 
 __all__ = ["get_latest_model_path", "load_model_checkpoint", "load_diffusion_checkpoint",
-           "save_diffusion_checkpoint"]
+           "save_diffusion_checkpoint", "load_fid_classifier"]
 
 
 def get_latest_model_path(ckpnt_path: str) -> str:
@@ -47,6 +47,19 @@ def load_diffusion_checkpoint(diffusion: torch.nn.Module, load_path: str, strict
     sd = ckpt["model"] if isinstance(ckpt, dict) and "model" in ckpt else ckpt
     diffusion.load_state_dict(sd, strict=strict)
     return ckpt
+
+
+def load_fid_classifier(path_or_folder: str, device: Any):
+    """The FID classifier of the reference's H36M evaluation (``src/metrics/fid.py:80-89``
+    ``get_classifier``): ``<folder>/h36m_classifier.pth`` (or the file itself), a ``{'model':
+    state_dict}`` of ``ClassifierForFID``, read with the tensor-only loader and bound to the HIP
+    engine as a ``metrics.FIDClassifier`` on `device`."""
+    from .metrics import FIDClassifier
+
+    path = os.path.join(path_or_folder, "h36m_classifier.pth") if os.path.isdir(path_or_folder) else path_or_folder
+    ckpt = load_model_checkpoint(path)
+    sd = ckpt["model"] if isinstance(ckpt, dict) and "model" in ckpt else ckpt
+    return FIDClassifier(sd, device)
 
 
 def save_diffusion_checkpoint(diffusion: torch.nn.Module, path: str, epoch: Optional[int] = None,

@@ -167,5 +167,19 @@ def get_stats_funcs(stats_mode, skeleton_key, **kwargs):
     raise NotImplementedError(f"stats_mode not implemented: {stats_mode}")
 
 
+def get_fid_storer(classifier_path=None, if_consider_hip=False, device="cuda", **kwargs):
+    """config_metrics.py:58-60 `get_fid_storer` with fid.py:80-89 `get_classifier`, without ignite:
+    (a `metrics.FIDAccumulator` over `<classifier_path>/h36m_classifier.pth`, the `(pred, target)`
+    selector of the evaluation dict).  `classifier_path` defaults to the reference's
+    `precomputed_folder` entry of the config.  Per batch: `acc.update(*select(**out))`; at the end
+    `acc.compute()`."""
+    from . import checkpoint
+
+    assert not if_consider_hip, "The skeleton should not consider hip to use the classifier."
+    path = classifier_path if classifier_path is not None else kwargs["precomputed_folder"]
+    acc = metrics.FIDAccumulator(checkpoint.load_fid_classifier(path, device))
+    return acc, lambda pred, target, **kwgs: (pred, target)
+
+
 __all__ = ["get_diffusion_latent_codes", "decode_latent_pred", "get_prediction", "process_evaluation_pair",
-           "long_term_prediction_best_every50", "long_term_prediction_best_first50", "get_stats_funcs"]
+           "long_term_prediction_best_every50", "long_term_prediction_best_first50", "get_stats_funcs", "get_fid_storer"]

@@ -20,6 +20,12 @@ reduction != 'mean'), reduced in a fixed order (deterministic).
     realism(pred, target, limbseq, limb_angles_idx)  all of the four lines above from one read of pred
                                       (sd_realism_target + sd_realism; float64 inside)
 
+    FIDClassifier(state_dict, device) fid_classifier.py:5-57  get_fid_features / features: the 2-layer GRU
+                                      classifier's 30 activations per future, one persistent launch (sd_fid_features)
+    FIDAccumulator(classifier)        fid.py:91-129          update / merge / all_reduce / reset / compute: float64
+                                      (count, sum x, sum x x^T) on the device (sd_fid_stats_update)
+    frechet_distance(mu1, s1, mu2, s2)  fid.py:17-68         host, float64, eigenvalues instead of scipy's sqrtm
+
 Up to 64 samples per sequence (the release evaluation draws 50); up to 64 joints, limbs and angle pairs.
 
 cmd(val_per_frame, val_ref) (multimodal.py:10-13) is the one host-side function here: the CMD score of
@@ -361,6 +367,178 @@ def motion_for_cmd(pred: torch.Tensor) -> torch.Tensor:
     return motion
 
 
+# ---- FID (sd_fid_features + sd_fid_stats_update) -----------------------------------------
+_FID_KEYS = ("recurrent.weight_ih_l0", "recurrent.weight_hh_l0", "recurrent.bias_ih_l0", "recurrent.bias_hh_l0",
+             "recurrent.weight_ih_l1", "recurrent.weight_hh_l1", "recurrent.bias_ih_l1", "recurrent.bias_hh_l1",
+             "linear1.weight", "linear1.bias")
+FID_HIDDEN = 128
+
+
+class FIDClassifier:
+    """The reference's `ClassifierForFID` (src/metrics/fid_classifier.py:5-57) as far as FID uses it:
+    `get_fid_features`, i.e. nn.GRU(input_size, 128, 2) over the frames and tanh(linear1(h_last)), as
+    one persistent HIP launch per call (sd_fid_features).  Built from the reference's state_dict
+    (`recurrent.weight_ih_l0` ... `recurrent.bias_hh_l1`, `linear1.*`; `linear2.*` is accepted and
+    unused: FID does not read the class scores)."""
+
+    def __init__(self, state_dict, device):
+        self.device = torch.device(device)
+        missing = [k for k in _FID_KEYS if k not in state_dict]
+        if missing:
+            raise KeyError(f"FIDClassifier: state_dict lacks {missing}")
+        self._w = {k: state_dict[k].detach().to(self.device, torch.float32).contiguous() for k in _FID_KEYS}
+        self.hidden_size = int(self._w["recurrent.weight_hh_l0"].shape[1])
+        self.input_size = int(self._w["recurrent.weight_ih_l0"].shape[1])
+        self.feat_size = int(self._w["linear1.weight"].shape[0])
+        shapes = {"recurrent.weight_ih_l0": (3 * self.hidden_size, self.input_size), "linear1.weight": (self.feat_size, self.hidden_size),
+                  "linear1.bias": (self.feat_size,)}
+        for k in _FID_KEYS:
+            want = shapes.get(k, (3 * self.hidden_size, self.hidden_size) if "weight" in k else (3 * self.hidden_size,))
+            if tuple(self._w[k].shape) != want:
+                raise ValueError(f"FIDClassifier: {k} has shape {tuple(self._w[k].shape)}, expected {want}")
+        self._desc = _lib.SDFidClassifierDesc(self.input_size, self.hidden_size, self.feat_size,
+                                              *(self._w[k].data_ptr() for k in _FID_KEYS))
+        self._ws = None
+
+    def initHidden(self, num_samples: int) -> torch.Tensor:
+        """fid_classifier.py:56-57: a fresh draw from torch's generator of the device per call."""
+        return torch.randn(2, num_samples, self.hidden_size, device=self.device)
+
+    def features(self, x: torch.Tensor, hidden_unit=None) -> torch.Tensor:
+        """x (..., frames, J, 3) or (rows, frames, input_size), as the pipeline holds it (a contiguous
+        float32 tensor is read in place) -> (rows, feat_size) float32.  hidden_unit (2, rows, 128) is
+        used as given; None draws `initHidden(rows)`."""
+        if self.device.type != "cuda" or not torch.is_tensor(x) or x.device.type != "cuda":
+            raise SkelDiffError("FIDClassifier: the classifier runs on the MI355X HIP engine only; build it on, and "
+                                "pass, a ROCm device")
+        if x.dim() >= 4 and x.shape[-1] * x.shape[-2] == self.input_size:
+            rows, frames = _flat(x.shape[:-3]), int(x.shape[-3])
+        elif x.dim() == 3 and x.shape[-1] == self.input_size:
+            rows, frames = int(x.shape[0]), int(x.shape[1])
+        else:
+            raise ValueError(f"FIDClassifier: (..., frames, J, 3) with 3 J = {self.input_size} or (rows, frames, "
+                             f"{self.input_size}) expected, got {tuple(x.shape)}")
+        x = _device_tensor(x, "motion")
+        if hidden_unit is None:
+            hidden_unit = self.initHidden(rows)
+        h0 = _device_tensor(hidden_unit, "hidden_unit")
+        if tuple(h0.shape) != (2, rows, self.hidden_size):
+            raise ValueError(f"FIDClassifier: hidden_unit {tuple(h0.shape)}, expected {(2, rows, self.hidden_size)}")
+        L = _lib.lib()
+        if self._ws is None:
+            self._ws = torch.empty(max(int(L.sd_fid_workspace_bytes(ctypes.byref(self._desc), rows)), 1), device=self.device,
+                                   dtype=torch.uint8)
+        feats = torch.empty(rows, self.feat_size, device=self.device, dtype=torch.float32)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        check(L.sd_fid_features(ctypes.byref(self._desc), x.data_ptr(), rows, frames, h0.data_ptr(), feats.data_ptr(),
+                                self._ws.data_ptr(), self._ws.numel(), stream))
+        return feats
+
+    def get_fid_features(self, motion_sequence: torch.Tensor, hidden_unit=None) -> torch.Tensor:
+        """fid_classifier.py:38-53 with its argument layout: motion_sequence (b, input_size, frames).
+        The permuted view the reference's storer passes (fid.py:113, :117) is read where it lies."""
+        return self.features(motion_sequence.permute(0, 2, 1), hidden_unit)
+
+
+def frechet_distance(mu1, sigma1, mu2, sigma2) -> float:
+    """fid.py:17-68 `_calculate_frechet_distance` on the host in float64, without scipy:
+    |mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr sqrt(S1 S2), the last trace as the sum of the square roots of
+    the eigenvalues of S1 S2 (real parts, clamped at 0: the product of two PSD matrices has real
+    non-negative eigenvalues up to rounding)."""
+    mu1, mu2 = (torch.atleast_1d(torch.as_tensor(m)).cpu() for m in (mu1, mu2))  # float32 means subtract in float32
+    s1, s2 = (torch.atleast_2d(torch.as_tensor(s, dtype=torch.float64)).cpu() for s in (sigma1, sigma2))
+    assert mu1.shape == mu2.shape, "Training and test mean vectors have different lengths"
+    assert s1.shape == s2.shape, "Training and test covariances have different dimensions"
+    diff = (mu1 - mu2).to(torch.float64)
+    ev = torch.linalg.eigvals(s1 @ s2).real.clamp_min(0.0)
+    return float(diff.dot(diff) + torch.trace(s1) + torch.trace(s2) - 2.0 * ev.sqrt().sum())
+
+
+class FIDAccumulator:
+    """The reference's `MetricStorerFID` (fid.py:91-129) without the host: `update` queues the two
+    feature passes and folds their activations into two float64 states (count, sum x, sum x x^T) on
+    the device; `compute` copies the 2 x (1 + feat + feat^2) doubles once.  `classifier` None (with
+    `feat_size`, `device`) gives a statistics-only accumulator for `merge` / `all_reduce`."""
+
+    def __init__(self, classifier=None, feat_size=None, device=None):
+        self.classifier = classifier
+        self.feat_size = int(classifier.feat_size if classifier is not None else feat_size)
+        self.device = torch.device(classifier.device if classifier is not None else (device or "cpu"))
+        n = 1 + self.feat_size + self.feat_size ** 2
+        self.state_pred = torch.zeros(n, dtype=torch.float64, device=self.device)
+        self.state_gt = torch.zeros(n, dtype=torch.float64, device=self.device)
+
+    def reset(self) -> None:
+        self.state_pred.zero_()
+        self.state_gt.zero_()
+
+    def _fold(self, feats: torch.Tensor, state: torch.Tensor) -> None:
+        L = _lib.lib()
+        rows = feats.shape[0]
+        ws = torch.empty(max(int(L.sd_fid_stats_workspace_bytes(rows, self.feat_size)), 1), device=feats.device,
+                         dtype=torch.uint8)
+        stream = torch.cuda.current_stream(feats.device).cuda_stream
+        check(L.sd_fid_stats_update(feats.data_ptr(), rows, self.feat_size, state.data_ptr(), ws.data_ptr(), ws.numel(),
+                                    stream))
+
+    def update_features(self, pred_feats=None, gt_feats=None) -> None:
+        """Fold (rows, feat_size) float32 device activations into the states."""
+        for f, st in ((pred_feats, self.state_pred), (gt_feats, self.state_gt)):
+            if f is not None:
+                f = _device_tensor(f, "features")
+                if f.dim() != 2 or f.shape[1] != self.feat_size:
+                    raise ValueError(f"FIDAccumulator: features (rows, {self.feat_size}) expected, got {tuple(f.shape)}")
+                self._fold(f, st)
+
+    def update(self, pred, target, hidden_unit_pred=None, hidden_unit_gt=None) -> None:
+        """fid.py:106-123: pred (B, S, T, J, 3), target (B, T, J, 3).  The predictions' features come
+        first, then the ground truth's (the reference's call order, so its randn order).  Everything
+        is queued on the current stream; nothing is copied to the host."""
+        if self.classifier is None:
+            raise SkelDiffError("FIDAccumulator: built without a classifier (statistics only)")
+        fp = self.classifier.features(pred, hidden_unit_pred)
+        fg = self.classifier.features(target, hidden_unit_gt)
+        self._fold(fp, self.state_pred)
+        self._fold(fg, self.state_gt)
+
+    def merge(self, other: "FIDAccumulator") -> "FIDAccumulator":
+        self.state_pred += other.state_pred.to(self.device)
+        self.state_gt += other.state_gt.to(self.device)
+        return self
+
+    def all_reduce(self, group=None) -> "FIDAccumulator":
+        """Sum the states over the ranks (RCCL for device states, gloo for host ones)."""
+        import torch.distributed as dist
+
+        both = torch.stack([self.state_pred, self.state_gt])
+        dist.all_reduce(both, op=dist.ReduceOp.SUM, group=group)
+        self.state_pred.copy_(both[0])
+        self.state_gt.copy_(both[1])
+        return self
+
+    @staticmethod
+    def statistics(state):
+        """(mu float32, sigma float64) of one state: `np.mean` of float32 activations
+        (a float32 result) and `np.cov(rowvar=False)` (float64, unbiased), fid.py:7-11."""
+        st = torch.as_tensor(state).detach().to("cpu", torch.float64)
+        F = int(round((-1 + (1 + 4 * (st.numel() - 1)) ** 0.5) / 2))
+        n = float(st[0])
+        if n < 2:
+            raise ValueError(f"FID needs at least 2 rows per side for a covariance, got {int(n)}")
+        sx, sxx = st[1:1 + F], st[1 + F:].reshape(F, F)
+        mean = sx / n
+        sigma = (sxx - torch.outer(sx, sx) / n) / (n - 1.0)
+        return mean.to(torch.float32), sigma
+
+    def compute(self) -> float:
+        """fid.py:125-129: `fid(gt activations, pred activations)` as a Python float."""
+        both = torch.stack([self.state_gt, self.state_pred]).cpu()  # the one device-to-host copy
+        mu_g, sg_g = self.statistics(both[0])
+        mu_p, sg_p = self.statistics(both[1])
+        return frechet_distance(mu_g, sg_g, mu_p, sg_p)
+
+
 __all__ = ["lat_apd", "apd", "ade", "fde", "mmade", "mmfde", "cmd", "mpjpe", "best_sample", "get_best_sample_idx",
            "choose_best_sample", "limb_stretching_normed_rmse", "limb_stretching_normed_mean", "limb_jitter_normed_rmse",
-           "limb_jitter_normed_mean", "mae", "motion_for_cmd", "realism", "Realism"]
+           "limb_jitter_normed_mean", "mae", "motion_for_cmd", "realism", "Realism", "FIDClassifier", "FIDAccumulator",
+           "frechet_distance"]

@@ -14,7 +14,12 @@ last 30 frames fed back, with per-segment stage times and the total.
 With --realism the fused body-realism / limb-angle / motion-profile call (metrics.realism)
 runs after the existing metrics on the same decoded futures, and its milliseconds are reported.
 
-Usage: python tools/eval_pipeline.py [sequences] [T] [--long-term FACTOR] [--realism]"""
+With --fid the pipeline runs at the H36M shape the FID classifier is trained for (J = 16, 25 observed and 100
+predicted frames) and ends with the FID accumulation (metrics.FIDAccumulator, DESIGN.md §4p: the classifier's
+features of the 50 futures and of the ground truth, folded into the running statistics) on synthetic
+classifier weights; its milliseconds and the FID value are reported.
+
+Usage: python tools/eval_pipeline.py [sequences] [T] [--long-term FACTOR] [--realism] [--fid]"""
 import json
 import sys
 import time
@@ -31,6 +36,9 @@ ARGS = sys.argv[1:]
 REALISM = "--realism" in ARGS
 if REALISM:
     ARGS.remove("--realism")
+FID = "--fid" in ARGS
+if FID:
+    ARGS.remove("--fid")
 LONG_TERM = None
 if "--long-term" in ARGS:
     _i = ARGS.index("--long-term")
@@ -38,10 +46,11 @@ if "--long-term" in ARGS:
     del ARGS[_i:_i + 2]
 NSEQ = int(ARGS[0]) if len(ARGS) > 0 else 256
 T = int(ARGS[1]) if len(ARGS) > 1 else 10
-FUT, OBS, PH = 50, 30, 120
+FUT, OBS, PH = (50, 25, 100) if FID else (50, 30, 120)
+SKEL = "h36m16" if FID else "amass21"
 cuda = torch.device("cuda:0")
-d, _, _ = build_config("amass21", cuda, T=T, batch=1, futures=FUT)
-_, _, _, types = skeleton("amass21")
+d, _, _ = build_config("amass16" if FID else "amass21", cuda, T=T, batch=1, futures=FUT)
+_, _, _, types = skeleton(SKEL)
 J = len(types)
 ae = AutoEncoder(node_types=torch.from_numpy(types), num_nodes=J, encoder_hidden_size=96, decoder_hidden_size=96,
                  latent_size=96, input_size=3, z_activation="tanh", enc_num_layers=1, output_size=3,
@@ -51,11 +60,20 @@ synthetic.fill_module_(ae, 4321)
 ae = ae.to(cuda)
 obs = (torch.from_numpy(synthetic.normal((NSEQ, OBS, J, 3), seed=51)) * 0.3).to(cuda)
 target = (torch.from_numpy(synthetic.normal((NSEQ, PH, J, 3), seed=52)) * 0.3).to(cuda)
+fid_acc = None
+if FID:  # tests/golden/gen_golden_fid.py's weight recipe: unsaturated activations
+    _shapes = {"linear1.weight": (30, 128), "linear1.bias": (30,)}
+    for _l, _k in ((0, 3 * J), (1, 128)):
+        _shapes.update({f"recurrent.weight_ih_l{_l}": (384, _k), f"recurrent.weight_hh_l{_l}": (384, 128),
+                        f"recurrent.bias_ih_l{_l}": (384,), f"recurrent.bias_hh_l{_l}": (384,)})
+    fid_acc = metrics.FIDAccumulator(metrics.FIDClassifier(
+        {n: torch.from_numpy(synthetic.uniform(s, seed=100 + i, low=-0.15, high=0.15)) for i, (n, s) in enumerate(sorted(_shapes.items()))},
+        cuda))
 
 
 def run():
     st = {}
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(7)]
     ev[0].record()
     z_past = ae.get_past_embedding(obs)
     ev[1].record()
@@ -68,8 +86,12 @@ def run():
     ade = metrics.ade(target, p)
     fde = metrics.fde(target, p)
     ev[4].record()
-    real = metrics.realism(p, target, skeletons.limbseq("amass21"), skeletons.limb_angles_idx("amass21")) if REALISM else None
+    real = metrics.realism(p, target, skeletons.limbseq(SKEL), skeletons.limb_angles_idx(SKEL)) if REALISM else None
     ev[5].record()
+    if FID:
+        fid_acc.reset()
+        fid_acc.update(p, target)
+    ev[6].record()
     torch.cuda.synchronize()
     for k, (a, b) in zip(("encode", "sample", "decode", "metrics"), zip(ev, ev[1:])):
         st[k] = a.elapsed_time(b)
@@ -80,6 +102,9 @@ def run():
                                 "StretchRMSE": 100 * float(real.srmse_std_mean.mean()),
                                 "JitterRMSE": 100 * float(real.jrmse_std_mean.mean()),
                                 "motion_mean": float(real.motion.mean())}
+    if FID:
+        st["fid"] = ev[5].elapsed_time(ev[6])
+        st["fid_value"] = fid_acc.compute()
     return st, float(apd.mean()), float(ade.mean()), float(fde.mean())
 
 
