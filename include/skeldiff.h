@@ -348,6 +348,29 @@ size_t sd_fid_stats_workspace_bytes(int64_t rows, int32_t feat);
 int sd_fid_stats_update(const float* feats, int64_t rows, int32_t feat, double* state, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* Multimodal ground truth (reference src/data/loaders/base/math_utils.py:59-110 get_multimodal_gt, whose
+ * get_mmgt_idxs (:60-65) is torch.cdist(seq1, seq2, p=2, compute_mode='donot_use_mm_for_euclid_dist'), and the
+ * APD of a segment's set of similar futures, src/metrics/multimodal.py:15-35 apd applied to the set: the
+ * quantity behind the reference's shipped mmapd_GT.csv, src/metrics/apde.py:9-48).
+ * sd_cdist: dist[i, j] = sqrt(sum_k (x1[i,k] - x2[j,k])^2), direct differences, f32;
+ *   x1 (m, features), x2 (n, features), dist (m, n) dense; 4-byte aligned, 16-byte accesses where the
+ *   addresses allow (an operand whose rows all start on a 16-byte boundary: an aligned base and features % 4
+ *   == 0; dist likewise with n % 4 == 0).  m == 0 or n == 0 launches nothing.
+ *   The value of dist[i, j] is a function of the two rows' contents and `features` only: the features are
+ *   summed in chunks of 32 from feature 0 on, inside a chunk t = fma(d_k, d_k, t) for k ascending from t = 0,
+ *   across chunks acc = acc + t in chunk order from acc = 0, then the correctly rounded square root.  So it
+ *   does not depend on m, n, the tile, pointer alignment or which operand is x1: sd_cdist(x, x) is bitwise
+ *   symmetric with an exactly zero diagonal, and row chunks give the bits of one call.
+ * sd_set_mean_distance: out[s] = mean over a < b in [row_ptr[s], row_ptr[s+1]) of dist[col[a] * n + col[b]]
+ *   (the reference's apd of the set, multimodal.py:15-35); 0 for a set of one member (multimodal.py:19-20),
+ *   NaN for an empty one.  dist (n, n) f32; row_ptr (nsets + 1) and col are DEVICE int64 arrays, every col
+ *   entry in [0, n).  float64 accumulation in a fixed order, f32 result.  nsets == 0 launches nothing.
+ * Negative sizes, features < 1 and a NULL pointer with a non-empty shape: SD_E_INVALID names the argument,
+ * before any launch. */
+int sd_cdist(const float* x1, int64_t m, const float* x2, int64_t n, int64_t features, float* dist, void* stream);
+int sd_set_mean_distance(const float* dist, int64_t n, const int64_t* row_ptr, const int64_t* col, int64_t nsets,
+                         float* out, void* stream);
+
 /* Test hooks: one kernel on caller buffers, for the per-kernel numerics tests.
  * sd_test_graph_linear: out(B,J,N) = act(FiLM(ghat @ (s_j W[type j] [x1_j | x2_j] + bias[type j]))) + res,
  *   W (types,N,K1+K2), bias (types,N) or NULL, ghat (J,J), film (2N) or NULL, res (B,J,N) or NULL,

@@ -43,6 +43,7 @@ EXPORTED = (
     "sd_pose_loss", "sd_test_set_split_route", "sd_chain_start", "sd_chain_tile_unit", "sd_best_sample",
     "sd_realism_target", "sd_realism", "sd_realism_frame_tile",
     "sd_fid_workspace_bytes", "sd_fid_features", "sd_fid_stats_workspace_bytes", "sd_fid_stats_update",
+    "sd_cdist", "sd_set_mean_distance",
 )
 
 # sd_plan_set_option keys (include/skeldiff.h)
@@ -179,6 +180,8 @@ def _declare(lib: ctypes.CDLL) -> None:
         "sd_fid_features": (ctypes.c_int, [ctypes.POINTER(SDFidClassifierDesc), vp, i64, i32, vp, vp, vp, sz, vp]),
         "sd_fid_stats_workspace_bytes": (sz, [i64, i32]),
         "sd_fid_stats_update": (ctypes.c_int, [vp, i64, i32, vp, vp, sz, vp]),
+        "sd_cdist": (ctypes.c_int, [vp, i64, vp, i64, i64, vp, vp]),
+        "sd_set_mean_distance": (ctypes.c_int, [vp, i64, vp, vp, i64, vp, vp]),
         "sd_profile_step": (ctypes.c_int, [vp, vp, vp, i64, i32, i64, vp, sz, i32, ctypes.POINTER(ctypes.c_float),
                                            ctypes.POINTER(ctypes.c_int32), vp]),
     }

@@ -181,5 +181,25 @@ def get_fid_storer(classifier_path=None, if_consider_hip=False, device="cuda", *
     return acc, lambda pred, target, **kwgs: (pred, target)
 
 
+def get_apde_storer(annotations_folder=None, gt_apd=None, device="cuda", **kwargs):
+    """config_metrics.py:55-56 `get_apde_storer` without ignite: (a factory of `metrics.APDEAccumulator`, the
+    `pred -> apd(pred)` transform of the evaluation dict).  The table is `gt_apd` (a tensor, e.g.
+    `MultimodalGT.gt_apd(futures)`) or `<annotations_folder>/mmapd_GT.csv`, the reference's file.  Per batch:
+    `acc.update(transform(**out))`; at the end `acc.compute()`.  The factory takes and ignores the reference's
+    `output_transform` keyword."""
+    import os
+
+    if gt_apd is None and annotations_folder is None:
+        raise ValueError("get_apde_storer: give gt_apd or annotations_folder")
+
+    def factory(output_transform=None, **kw):
+        if gt_apd is not None:
+            return metrics.APDEAccumulator(gt_apd, device)
+        return metrics.APDEAccumulator.from_csv(os.path.join(annotations_folder, "mmapd_GT.csv"), device)
+
+    return factory, lambda pred, **kwgs: metrics.apd(pred)
+
+
 __all__ = ["get_diffusion_latent_codes", "decode_latent_pred", "get_prediction", "process_evaluation_pair",
-           "long_term_prediction_best_every50", "long_term_prediction_best_first50", "get_stats_funcs", "get_fid_storer"]
+           "long_term_prediction_best_every50", "long_term_prediction_best_first50", "get_stats_funcs", "get_fid_storer",
+           "get_apde_storer"]

@@ -25,6 +25,8 @@ reduction != 'mean'), reduced in a fixed order (deterministic).
     FIDAccumulator(classifier)        fid.py:91-129          update / merge / all_reduce / reset / compute: float64
                                       (count, sum x, sum x x^T) on the device (sd_fid_stats_update)
     frechet_distance(mu1, s1, mu2, s2)  fid.py:17-68         host, float64, eigenvalues instead of scipy's sqrtm
+    APDEAccumulator(gt_apd)           apde.py:9-48           update / merge / all_reduce / reset / compute: mean
+                                      |APD(pred) - APD(multimodal gt)|; the table: multimodal_gt.MultimodalGT.gt_apd
 
 Up to 64 samples per sequence (the release evaluation draws 50); up to 64 joints, limbs and angle pairs.
 
@@ -538,7 +540,96 @@ class FIDAccumulator:
         return frechet_distance(mu_g, sg_g, mu_p, sg_p)
 
 
+# ---- APDE (the table: multimodal_gt.MultimodalGT.gt_apd) -----------------------------------------
+class APDEAccumulator:
+    """The reference's `MetricStorerAPDE` (src/metrics/apde.py:9-48) on the device: the mean over the test
+    segments of |APD(pred) - APD(multimodal ground truth)|, skipping segments whose ground-truth APD is 0
+    (they become NaN, apde.py:18) or NaN.  `gt_apd` is the per-segment table (`MultimodalGT.gt_apd`, or
+    `from_csv` for the reference's mmapd_GT.csv) in the order the evaluation visits the segments; `ids`
+    (optional) the segment number of every entry, for updates by index when that order is not 0, 1, 2, ...
+    State: a float64 sum and an int64 count on `device`; torch ops only (not a hot path)."""
+
+    def __init__(self, gt_apd, device=None, ids=None):
+        g = torch.as_tensor(gt_apd)
+        self.device = torch.device(device) if device is not None else g.device
+        g = g.detach().to(self.device, torch.float64).reshape(-1)
+        self.gt_apd = torch.where(g == 0, torch.full_like(g, float("nan")), g)
+        self._pos = None
+        if ids is not None:
+            ids = torch.as_tensor(ids, dtype=torch.int64).reshape(-1)
+            if ids.numel() != g.numel():
+                raise ValueError(f"APDEAccumulator: {ids.numel()} ids for {g.numel()} values")
+            if not torch.equal(ids.cpu(), torch.arange(g.numel())):
+                self._pos = torch.full((int(ids.max()) + 1,), -1, dtype=torch.int64)
+                self._pos[ids.cpu()] = torch.arange(g.numel())
+                self._pos = self._pos.to(self.device)
+        self.sum = torch.zeros((), dtype=torch.float64, device=self.device)
+        self.count = torch.zeros((), dtype=torch.int64, device=self.device)
+        self.index = 0
+
+    @classmethod
+    def from_csv(cls, path, device="cpu") -> "APDEAccumulator":
+        """apde.py:17: the `gt_APD` column of an `id,gt_APD` file (the first column is the index), rows in file order."""
+        import csv
+
+        with open(path, newline="") as f:
+            rows = list(csv.reader(f))
+        head = rows[0]
+        if "gt_APD" not in head:
+            raise ValueError(f"{path}: no gt_APD column in {head}")
+        c = head.index("gt_APD")
+        body = [r for r in rows[1:] if r]
+        values = [float(r[c]) if r[c] != "" else float("nan") for r in body]
+        return cls(torch.tensor(values, dtype=torch.float64), device, ids=[int(r[0]) for r in body])
+
+    def reset(self) -> None:
+        self.sum.zero_()
+        self.count.zero_()
+        self.index = 0
+
+    def update(self, apd_pred: torch.Tensor, segment_idx=None) -> None:
+        """apde.py:29-41: apd_pred (B,) the batch's `metrics.apd(pred)`.  Without segment_idx the next B table
+        entries are consumed, as the reference; with it (segment numbers; a list or a tensor) entry by index,
+        for a sharded evaluation.  Nothing is copied to the host."""
+        a = torch.as_tensor(apd_pred).detach().to(self.device, torch.float64).reshape(-1)
+        B = a.numel()
+        if segment_idx is None:
+            if self.index + B > self.gt_apd.numel():
+                raise ValueError(f"APDEAccumulator: {self.index + B} predictions for a table of {self.gt_apd.numel()}")
+            g = self.gt_apd[self.index:self.index + B]
+            self.index += B
+        else:
+            idx = torch.as_tensor(segment_idx, dtype=torch.int64).to(self.device).reshape(-1)
+            if idx.numel() != B:
+                raise ValueError(f"APDEAccumulator: {idx.numel()} indices for {B} predictions")
+            g = self.gt_apd[idx if self._pos is None else self._pos[idx]]
+        err = (a - g).abs()
+        ok = ~torch.isnan(err)
+        self.sum += torch.where(ok, err, torch.zeros_like(err)).sum()
+        self.count += ok.sum()
+
+    def merge(self, other: "APDEAccumulator") -> "APDEAccumulator":
+        self.sum += other.sum.to(self.device)
+        self.count += other.count.to(self.device)
+        return self
+
+    def all_reduce(self, group=None) -> "APDEAccumulator":
+        """Sum the states over the ranks (RCCL for device states, gloo for host ones); a count is exact in float64."""
+        import torch.distributed as dist
+
+        both = torch.stack([self.sum, self.count.to(torch.float64)])
+        dist.all_reduce(both, op=dist.ReduceOp.SUM, group=group)
+        self.sum.copy_(both[0])
+        self.count.copy_(both[1].to(torch.int64))
+        return self
+
+    def compute(self) -> float:
+        """apde.py:43-48: sum / count as a Python float (NaN before any counted segment): the one copy to the host."""
+        s, c = torch.stack([self.sum, self.count.to(torch.float64)]).cpu().tolist()
+        return s / c if c else float("nan")
+
+
 __all__ = ["lat_apd", "apd", "ade", "fde", "mmade", "mmfde", "cmd", "mpjpe", "best_sample", "get_best_sample_idx",
            "choose_best_sample", "limb_stretching_normed_rmse", "limb_stretching_normed_mean", "limb_jitter_normed_rmse",
            "limb_jitter_normed_mean", "mae", "motion_for_cmd", "realism", "Realism", "FIDClassifier", "FIDAccumulator",
-           "frechet_distance"]
+           "frechet_distance", "APDEAccumulator"]
