@@ -546,6 +546,44 @@ int sd_film_tanh_backward(const float* y, const float* ss, const float* out, con
 int sd_l1norm_rows_forward(const float* G, float* ghat, int32_t J, int32_t count, float eps, void* stream);
 int sd_l1norm_rows_backward(const float* G, const float* dghat, float* dG, int32_t J, int32_t count, float eps,
                             void* stream);
+/* Training-side graph-GRU: the recurrent core of StaticGraphGRUCell.forward unrolled
+ * over a sequence by StaticGraphGRU.forward / Decoder.forward (reference
+ * src/core/network/layers/recurrent.py:321-366 and :369-391, src/core/network/nn/decoder.py:85-104,
+ * clockwork off) and the backward torch autograd derives for it in AutoEncoderTrainer.train_step
+ * (src/core/trainer.py:79-96).  Caller-owned device buffers, row-major f32:
+ *   a (rows, Ta, J, 3H) = W_ih x + b_ih, unmixed; Ta = T (one projection per frame) or 1 (one
+ *   projection reused at every step), h0 (rows, J, H), gx (Tg, J, J) the mixing matrix per step,
+ *   Tg = T or 1, W_hh (types, 3H, H), b_hh (types, 3H) or NULL, node_types HOST int64 (J) with
+ *   values in [0, n_types) (n_types = 0: shared weights, W_hh (1, 3H, H), node_types ignored).
+ * sd_gru_train_forward: hs (rows, T, J, H), the hidden state after each step.  With hprev
+ *   (rows, T, J, H), c (rows, T, J, 3H) and gates (rows, T, J, 4H) given (all three or none) it keeps
+ *   the state backward reads: h_{t-1}, c_t = W_hh h_{t-1} + b_hh and [r | z | n | (gx c)_n].
+ * sd_gru_train_backward: from dhs (rows, T, J, H) and that state: da (rows, Ta, J, 3H) (summed over
+ *   the steps when Ta = 1), dh0 (rows, J, H), dgx (Tg, J, J) (per step when Tg = T), dW_hh, db_hh;
+ *   any output may be NULL (not computed).  Every reduction over rows and steps runs in a fixed
+ *   order (no float atomics): repeated calls give the same bits.
+ * Both need workspace >= sd_gru_train_workspace_bytes(rows, T, J, H, n_types).
+ * Checked on the host before any device call (SD_E_INVALID names the argument): NULL pointers, J
+ * outside 1..64, H not a positive multiple of 16 (at most 256), T < 1, Ta / Tg not in {1, T}, node
+ * types out of range, a short workspace.  rows == 0: SD_OK (the backward zeroes dgx, dW_hh, db_hh). */
+size_t sd_gru_train_workspace_bytes(int64_t rows, int32_t T, int32_t J, int32_t H, int32_t n_types);
+int sd_gru_train_forward(const float* a, int32_t Ta, const float* h0, const float* gx, int32_t Tg, const float* W_hh,
+                         const float* b_hh, const int64_t* node_types, int32_t n_types, int64_t rows, int32_t T,
+                         int32_t J, int32_t H, float* hs, float* hprev, float* c, float* gates, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int sd_gru_train_backward(const float* dhs, const float* a, int32_t Ta, const float* gx, int32_t Tg, const float* W_hh,
+                          const int64_t* node_types, int32_t n_types, const float* hprev, const float* c,
+                          const float* gates, int64_t rows, int32_t T, int32_t J, int32_t H, float* da, float* dh0,
+                          float* dgx, float* dW_hh, float* db_hh, void* workspace, size_t workspace_bytes, void* stream);
+/* The cell's mixing matrix per step under autograd (reference recurrent.py:333-334 and :361-364):
+ *   gxt[0] = normalize_L1(G) (normalize0 != 0: learn_influence) or G,
+ *   gxt[t + 1] = normalize_L1(gxt[t] + G_add), row-wise with F.normalize's eps; G_add NULL = 0.
+ * One launch each way, the steps in sequence inside the kernel.  gxt, dgxt (T, J, J); the backward
+ * reads the forward's gxt and writes dG and dG_add (NULL: not computed).  1 <= J <= 64, T >= 1. */
+int sd_gx_table_forward(const float* G, const float* G_add, int32_t J, int32_t T, int32_t normalize0, float eps,
+                        float* gxt, void* stream);
+int sd_gx_table_backward(const float* G, const float* G_add, const float* gxt, const float* dgxt, int32_t J, int32_t T,
+                         int32_t normalize0, float eps, float* dG, float* dG_add, void* stream);
 /* PreNorm's RMSNorm under autograd (reference attention.py:30-36): x (R, C), R vectors of C
  * features, out = x / max(||x||, eps) * g * scale (scale = sqrt(C)); the forward also writes
  * dnorm (R) = max(||x||, eps) for the backward, which writes dx (R, C) and dg (C), the latter

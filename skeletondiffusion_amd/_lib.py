@@ -44,6 +44,8 @@ EXPORTED = (
     "sd_realism_target", "sd_realism", "sd_realism_frame_tile",
     "sd_fid_workspace_bytes", "sd_fid_features", "sd_fid_stats_workspace_bytes", "sd_fid_stats_update",
     "sd_cdist", "sd_set_mean_distance",
+    "sd_gru_train_workspace_bytes", "sd_gru_train_forward", "sd_gru_train_backward", "sd_gx_table_forward",
+    "sd_gx_table_backward",
 )
 
 # sd_plan_set_option keys (include/skeldiff.h)
@@ -155,6 +157,13 @@ def _declare(lib: ctypes.CDLL) -> None:
         "sd_gl_train_forward": (ctypes.c_int, [vp, vp, vp, vp, i32, vp, i64, i32, i32, i32, vp, vp, vp]),
         "sd_gl_train_backward": (ctypes.c_int, [vp, vp, vp, vp, vp, i32, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp,
                                                 sz, vp]),
+        "sd_gru_train_workspace_bytes": (sz, [i64, i32, i32, i32, i32]),
+        "sd_gru_train_forward": (ctypes.c_int, [vp, i32, vp, vp, i32, vp, vp, ctypes.POINTER(i64), i32, i64, i32, i32, i32,
+                                                vp, vp, vp, vp, vp, sz, vp]),
+        "sd_gru_train_backward": (ctypes.c_int, [vp, vp, i32, vp, i32, vp, ctypes.POINTER(i64), i32, vp, vp, vp, i64, i32,
+                                                 i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "sd_gx_table_forward": (ctypes.c_int, [vp, vp, i32, i32, i32, ctypes.c_float, vp, vp]),
+        "sd_gx_table_backward": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, ctypes.c_float, vp, vp, vp]),
         "sd_attn_train_forward": (ctypes.c_int, [vp, vp, i64, i32, i32, i32, ctypes.c_float, vp]),
         "sd_attn_train_backward": (ctypes.c_int, [vp, vp, vp, i64, i32, i32, i32, ctypes.c_float, vp]),
         "sd_film_tanh_forward": (ctypes.c_int, [vp, vp, vp, i64, i32, i32, vp]),

@@ -8,7 +8,8 @@ state_dict keys as the reference, so its autoencoder checkpoints load strictly.
 106-116`), run on bs x 50 rows for ph frames -- goes to the HIP decoder (`sd_gru_decode`) and
 `get_past_embedding` (the conditioning latents) to the HIP encoder (`sd_gru_encode`) when the
 module lives on a ROCm device; on the CPU they raise (no CPU evaluation path).  `forward` /
-`autoencode` (training, autograd) stay torch ops.
+`autoencode` (stage-1 training, autograd) run each GRU as one HIP sequence call per forward
+(`training.graph_gru` / `gx_table`) on a ROCm device and stay torch ops on the CPU.
 """
 from __future__ import annotations
 
@@ -20,6 +21,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn import Parameter
 
+from ... import training as _training
 from .layers import StaticGraphLinear
 
 __all__ = ["StaticGraphGRUCell", "StaticGraphGRU", "Encoder", "Decoder", "AutoEncoder"]
@@ -156,6 +158,63 @@ class StaticGraphGRU(nn.Module):
         return output, output_states
 
 
+def _no_dropout(*mods) -> bool:
+    return all(m.p == 0.0 or not m.training for m in mods)
+
+
+def _hip_sequence_ok(rnn: "StaticGraphGRU", x: torch.Tensor, *dropouts) -> bool:
+    """Whether a GRU forward takes the HIP sequence path (training.graph_gru): fp32 tensors on a
+    ROCm device, the HIP training switch on, one layer, clockwork off, no active dropout, and a
+    cell the kernels cover.  Otherwise the torch ops below run, unchanged."""
+    if not (x.is_cuda and x.dtype == torch.float32 and _training.hip_training_enabled() and len(rnn.layers) == 1):
+        return False
+    cell = rnn.layers[0]
+    if cell.clockwork or not _no_dropout(cell.dropout, cell.r_dropout, rnn.dropout, *dropouts):
+        return False
+    H, J = cell.hidden_size, cell.num_nodes
+    if cell.weight_hh.dtype != torch.float32 or H % 16 or H > _training.GRU_MAX_HIDDEN or not 1 <= J <= _training.MAX_NODES:
+        return False
+    if x.shape[-2] != J:
+        return False
+    # a fixed additive matrix without re-normalisation (gx_t = G + t G_add) is not built
+    return not (isinstance(cell.G_add, torch.Tensor) and not (cell.learn_influence or cell.learn_additive_graph_influence))
+
+
+def _hip_linear(mod: StaticGraphLinear, x: torch.Tensor) -> torch.Tensor:
+    """A StaticGraphLinear through GraphLinearFunction whether or not grad is enabled (under
+    no_grad the same HIP forward runs and keeps nothing)."""
+    g = mod.ghat()
+    if mod.weight.dtype != torch.float32 or not mod._hip_ok(x, g):
+        return mod(x)
+    return _training.graph_linear(x, mod.weight, mod.bias, g, mod._node_types_on(x.device))
+
+
+def _hip_gru_sequence(cell: StaticGraphGRUCell, x: torch.Tensor, h0: torch.Tensor, steps: int):
+    """The cell over `steps` steps on HIP: x (B, Ta, J, D) with Ta = steps or 1 (the same input
+    at every step) -> hs (B, steps, J, H) and the mixing matrix after the last step."""
+    J = cell.num_nodes
+    dev = x.device
+    eye = getattr(cell, "_eye", None)
+    if eye is None or eye.device != dev:
+        eye = cell._eye = torch.eye(J, device=dev, dtype=torch.float32)
+    nt = cell.node_type_index
+    # unmixed input projections W_ih x + b_ih over all B Ta rows (identity mixing matrix)
+    a = _training.graph_linear(x, cell.weight_ih, cell.bias_ih, eye, nt)
+    if isinstance(cell.G_add, torch.Tensor):
+        table = _training.gx_table(cell.G, cell.G_add, steps + 1, normalize0=cell.learn_influence)
+        gx, gx_last = table[:steps], table[steps]
+    else:  # gx never changes: re-normalising an L1-normalised matrix is the identity
+        if not cell.learn_influence:
+            gx_last = cell.G
+        elif torch.is_grad_enabled():
+            gx_last = _training.l1norm_rows(cell.G, 1e-12)
+        else:
+            gx_last = F.normalize(cell.G, p=1., dim=1)
+        gx = gx_last.unsqueeze(0)
+    hs = _training.graph_gru(a, h0, gx, cell.weight_hh, cell.bias_hh, nt, steps=steps)
+    return hs, gx_last
+
+
 def _recurrent(arch: str):
     if arch != "StaticGraphGRU":
         raise NotImplementedError(f"recurrent arch {arch!r}: only StaticGraphGRU (the released configs) is built")
@@ -183,6 +242,11 @@ class Encoder(nn.Module):
         self.dropout = nn.Dropout(dropout)
 
     def forward(self, x: torch.Tensor, state=None):
+        if state is None and x.dim() == 4 and x.shape[1] >= 1 and _hip_sequence_ok(self.rnn, x, self.dropout):
+            # the whole sequence in one HIP call (forward + BPTT)
+            hs, gx = _hip_gru_sequence(self.rnn.layers[0], x, _hip_linear(self.initial_hidden1, x[:, 0]), x.shape[1])
+            h_last = hs[:, -1]
+            return self.activation_fn(_hip_linear(self.fc, h_last)), [(h_last, gx)]
         if state is None:
             state = [(self.initial_hidden1(x[:, 0]), None)] * self.num_layers
         y, state = self.rnn(input=x, states=state)
@@ -218,8 +282,15 @@ class Decoder(nn.Module):
         return torch.cat([x_t, h], dim=-1).unsqueeze(1), [(rnn_h, None)] * self.num_layers
 
     def forward(self, x: torch.Tensor, h: torch.Tensor, z: torch.Tensor, ph: int = 1, state=None):
-        """Torch forward (training / autograd); `AutoEncoder.decode` uses the HIP decoder."""
+        """Training forward (autograd): one HIP sequence call on a ROCm device, torch ops
+        otherwise; `AutoEncoder.decode` uses the HIP decoder."""
         x_t_s = x[:, -1].clone()
+        if ph >= 1 and _hip_sequence_ok(self.rnn, x, self.dropout):
+            x_t_1 = x[:, -2] if state is None else state
+            rnn_h = _hip_linear(self.initial_hidden_h, torch.cat([x_t_1, h], dim=-1))
+            rec_input = torch.cat([x[:, -1], h], dim=-1).unsqueeze(1)  # the same input at every step
+            hs, _ = _hip_gru_sequence(self.rnn.layers[0], rec_input, rnn_h, ph)
+            return self.activation_fn(_hip_linear(self.fc, hs)), x_t_s  # fc over all ph states at once
         rec_input, hidden = self.init_recurrent_hidden(x=x, h=h, z=z, state=state)
         out = []
         for i in range(ph):
@@ -283,7 +354,8 @@ class AutoEncoder(nn.Module):
         return self._hip().decode(x[:, -2:], h, ph)
 
     def autoencode(self, y, past, ph=1, state=None):
-        """Training-time reconstruction on torch ops (autograd)."""
+        """Training-time reconstruction (autograd): HIP sequence calls on a ROCm device, torch
+        ops on the CPU."""
         with torch.no_grad():
             z_past = self.z_activation(self(past))
         z = self.get_embedding(y, state=state)

@@ -12,9 +12,15 @@ src/core/trainer.py:224-276).  The mixing matrix's own gradient flows on through
 `StaticGraphLinear.forward` (core/network/layers.py) routes here when the input is an fp32 device
 tensor, grad is enabled and `hip_training_enabled()`; there is no silent CPU fallback on a GPU
 (the library must load or the call raises).
+
+`graph_gru` / `gx_table` are the graph-GRU sequence core and its per-step mixing matrices for
+stage-1 training of the motion autoencoder (`sd_gru_train_*`, `sd_gx_table_*`,
+csrc/sd_gru_train.hip), under the same switch.
 """
 from __future__ import annotations
 
+import collections
+import ctypes
 from typing import Optional
 
 import torch
@@ -197,6 +203,166 @@ def graph_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Ten
     if x.dtype != torch.float32 or weight.dtype != torch.float32:
         raise ValueError("graph_linear: the HIP training path is fp32")
     return GraphLinearFunction.apply(x, weight, bias, ghat, node_types)
+
+
+# ---- graph-GRU sequence core and gx table (reference recurrent.py:321-391) -------
+
+# launches of the sequence entries since import, by name (tests and tools read it as a spy)
+CALLS = collections.Counter()
+
+GRU_MAX_HIDDEN = 256  # sd_gru_train_*: H a positive multiple of 16, at most 256
+
+
+def _host_types(node_types, J: int):
+    """ctypes int64 array (or None) of a node-type vector for the entries that take it on the
+    host; one device-to-host copy per (tensor, version), not one per call."""
+    if node_types is None:
+        return None
+    key = (id(node_types), node_types._version)
+    hit = _HOST_TYPES.get(key)
+    if hit is None or hit[0] is not node_types:
+        vals = [int(v) for v in node_types.detach().cpu().reshape(-1).tolist()]
+        if len(vals) != J:
+            raise ValueError(f"node_types has {len(vals)} entries, the input {J} nodes")
+        if len(_HOST_TYPES) > 64:
+            _HOST_TYPES.clear()
+        hit = (node_types, (ctypes.c_int64 * J)(*vals))
+        _HOST_TYPES[key] = hit
+    return hit[1]
+
+
+_HOST_TYPES: dict = {}
+
+
+class GraphGRUFunction(torch.autograd.Function):
+    """hs = the StaticGraphGRU cell unrolled over T steps from the unmixed input projections
+    (`sd_gru_train_forward` / `_backward`, csrc/sd_gru_train.hip).  The state backward reads is
+    kept only when an input needs a gradient (under no_grad the same forward runs without it)."""
+
+    @staticmethod
+    def forward(ctx, a, h0, gx, weight_hh, bias_hh, node_types, T: int):
+        B, Ta, J, H3 = a.shape
+        H = H3 // 3
+        Tg = gx.shape[0]
+        ac, hc, gc = a.contiguous(), h0.contiguous(), gx.contiguous()
+        w3 = (weight_hh if weight_hh.dim() == 3 else weight_hh.unsqueeze(0)).contiguous()
+        n_types = int(w3.shape[0]) if node_types is not None else 0
+        b2 = None if bias_hh is None else bias_hh.reshape(w3.shape[0], H3).contiguous()
+        nt = _host_types(node_types, J)
+        dev = a.device
+        keep = any(ctx.needs_input_grad[:5])
+        hs = torch.empty(B, T, J, H, device=dev, dtype=torch.float32)
+        hprev = torch.empty_like(hs) if keep else None
+        c = torch.empty(B, T, J, H3, device=dev, dtype=torch.float32) if keep else None
+        gates = torch.empty(B, T, J, 4 * H, device=dev, dtype=torch.float32) if keep else None
+        L = _lib.lib()
+        ws_bytes = L.sd_gru_train_workspace_bytes(B, T, J, H, n_types)
+        ws = torch.empty(max(1, (ws_bytes + 3) // 4), device=dev, dtype=torch.float32)
+        CALLS["gru_forward"] += 1
+        _lib.check(L.sd_gru_train_forward(
+            ac.data_ptr(), Ta, hc.data_ptr(), gc.data_ptr(), Tg, w3.data_ptr(), _lib.ptr(b2), nt, n_types, B, T, J, H,
+            hs.data_ptr(), _lib.ptr(hprev), _lib.ptr(c), _lib.ptr(gates), ws.data_ptr(), ws_bytes, _stream(dev)))
+        if keep:
+            ctx.save_for_backward(ac, gc, w3, hprev, c, gates)
+            ctx.meta = (B, T, Ta, Tg, J, H, n_types, nt, weight_hh.shape, None if bias_hh is None else bias_hh.shape,
+                        a.shape, h0.shape, gx.shape)
+        return hs
+
+    @staticmethod
+    def backward(ctx, dhs):
+        ac, gc, w3, hprev, c, gates = ctx.saved_tensors
+        B, T, Ta, Tg, J, H, n_types, nt, wshape, bshape, ashape, hshape, gshape = ctx.meta
+        need_a, need_h, need_g, need_w, need_b = ctx.needs_input_grad[:5]
+        dev = ac.device
+        dc = dhs.contiguous().float()
+        da = torch.empty(B, Ta, J, 3 * H, device=dev) if need_a else None
+        dh0 = torch.empty(B, J, H, device=dev) if need_h else None
+        dgx = torch.empty(Tg, J, J, device=dev) if need_g else None
+        dW = torch.empty(w3.shape, device=dev) if need_w else None
+        db = torch.empty(w3.shape[0], 3 * H, device=dev) if (need_b and bshape is not None) else None
+        L = _lib.lib()
+        ws_bytes = L.sd_gru_train_workspace_bytes(B, T, J, H, n_types)
+        ws = torch.empty(max(1, (ws_bytes + 3) // 4), device=dev, dtype=torch.float32)
+        CALLS["gru_backward"] += 1
+        _lib.check(L.sd_gru_train_backward(
+            dc.data_ptr(), ac.data_ptr(), Ta, gc.data_ptr(), Tg, w3.data_ptr(), nt, n_types, hprev.data_ptr(),
+            c.data_ptr(), gates.data_ptr(), B, T, J, H, _lib.ptr(da), _lib.ptr(dh0), _lib.ptr(dgx), _lib.ptr(dW),
+            _lib.ptr(db), ws.data_ptr(), ws_bytes, _stream(dev)))
+        return (None if da is None else da.reshape(ashape), None if dh0 is None else dh0.reshape(hshape),
+                None if dgx is None else dgx.reshape(gshape), None if dW is None else dW.reshape(wshape),
+                None if db is None else db.reshape(bshape), None, None)
+
+
+def graph_gru(a: torch.Tensor, h0: torch.Tensor, gx: torch.Tensor, weight_hh: torch.Tensor,
+              bias_hh: Optional[torch.Tensor], node_types: Optional[torch.Tensor],
+              steps: Optional[int] = None) -> torch.Tensor:
+    """HIP graph-GRU core under autograd (fp32 device tensors; recurrent.py:321-366 unrolled,
+    clockwork off).  a (B, Ta, J, 3H) = the unmixed input projections W_ih x + b_ih, Ta = T or 1
+    (one projection reused at every step); h0 (B, J, H); gx (Tg, J, J) or (J, J), Tg = T or 1;
+    weight_hh (types, 3H, H) with node_types (J,), or (3H, H) shared with node_types None; bias_hh
+    or None.  `steps` = T (default: the larger of Ta and Tg).  Returns hs (B, T, J, H)."""
+    if not a.is_cuda or a.dtype != torch.float32 or weight_hh.dtype != torch.float32 or h0.dtype != torch.float32 \
+            or gx.dtype != torch.float32:
+        raise ValueError("graph_gru: the HIP training path needs fp32 device tensors")
+    if a.dim() != 4 or a.shape[-1] % 3 or h0.dim() != 3:
+        raise ValueError("graph_gru: a (B, Ta, J, 3H) and h0 (B, J, H)")
+    if gx.dim() == 2:
+        gx = gx.unsqueeze(0)
+    B, Ta, J, H3 = a.shape
+    H = H3 // 3
+    T = int(steps) if steps is not None else max(Ta, gx.shape[0])
+    if tuple(h0.shape) != (B, J, H) or gx.dim() != 3 or tuple(gx.shape[1:]) != (J, J):
+        raise ValueError("graph_gru: h0 must be (B, J, H) and gx (Tg, J, J)")
+    if (node_types is None) != (weight_hh.dim() == 2) or tuple(weight_hh.shape[-2:]) != (H3, H):
+        raise ValueError("graph_gru: weight_hh (types, 3H, H) with node_types, or (3H, H) without")
+    if bias_hh is not None and bias_hh.numel() != weight_hh.numel() // H:
+        raise ValueError("graph_gru: bias_hh must hold 3H values per weight type")
+    return GraphGRUFunction.apply(a, h0, gx, weight_hh, bias_hh, node_types, T)
+
+
+class GxTableFunction(torch.autograd.Function):
+    """gxt[0] = normalize_L1(G) or G, gxt[t + 1] = normalize_L1(gxt[t] + G_add), one HIP launch
+    each way (`sd_gx_table_forward` / `_backward`)."""
+
+    @staticmethod
+    def forward(ctx, G, G_add, steps: int, normalize0: bool, eps: float):
+        Gc = G.detach().contiguous()
+        Ac = None if G_add is None else G_add.detach().contiguous()
+        J = Gc.shape[0]
+        out = torch.empty(steps, J, J, device=G.device, dtype=torch.float32)
+        CALLS["gx_table_forward"] += 1
+        _lib.check(_lib.lib().sd_gx_table_forward(Gc.data_ptr(), _lib.ptr(Ac), J, steps, int(normalize0), float(eps),
+                                                  out.data_ptr(), _stream(G.device)))
+        ctx.save_for_backward(Gc, Ac, out)
+        ctx.meta = (J, steps, int(normalize0), float(eps))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        Gc, Ac, out = ctx.saved_tensors
+        J, steps, normalize0, eps = ctx.meta
+        need_add = Ac is not None and ctx.needs_input_grad[1]
+        dc = dout.contiguous().float()
+        dG = torch.empty_like(Gc)
+        dA = torch.empty_like(Gc) if need_add else None
+        CALLS["gx_table_backward"] += 1
+        _lib.check(_lib.lib().sd_gx_table_backward(Gc.data_ptr(), _lib.ptr(Ac), out.data_ptr(), dc.data_ptr(), J, steps,
+                                                   normalize0, eps, dG.data_ptr(), _lib.ptr(dA), _stream(Gc.device)))
+        return dG, dA, None, None, None
+
+
+def gx_table(G: torch.Tensor, G_add: Optional[torch.Tensor], steps: int, normalize0: bool = True,
+             eps: float = 1e-12) -> torch.Tensor:
+    """HIP table of the GRU cell's mixing matrix over `steps` steps under autograd
+    (recurrent.py:333-334, 361-364): (J, J) fp32 device matrices, J <= 64 -> (steps, J, J)."""
+    J = G.shape[0]
+    if not G.is_cuda or G.dtype != torch.float32 or G.dim() != 2 or tuple(G.shape) != (J, J) or J > MAX_NODES:
+        raise ValueError("gx_table: the HIP training path needs a (J, J) fp32 device matrix, J <= 64")
+    if G_add is not None and (G_add.dtype != torch.float32 or tuple(G_add.shape) != (J, J) or G_add.device != G.device):
+        raise ValueError("gx_table: G_add must match G")
+    if steps < 1:
+        raise ValueError("gx_table: steps must be >= 1")
+    return GxTableFunction.apply(G, G_add, int(steps), bool(normalize0), float(eps))
 
 
 class L1NormRowsFunction(torch.autograd.Function):
