@@ -609,6 +609,51 @@ int sd_mahalanobis_loss_backward(const float* model_out, const float* target, co
                                  int32_t T, const float* dloss, int64_t rows, int32_t J, int32_t F, int32_t pred_noise,
                                  int32_t mse, float* dmodel_out, void* stream);
 
+/* Fused optimizer step: what follows backward in the reference's two training loops,
+ * src/core/trainer.py:33 (AdamW, amsgrad) and :93-95 (clip_grad_norm_, step) of AutoEncoderTrainer,
+ * :153 (Adam), :159 (ema_pytorch.EMA) and :267-275 (clip_grad_norm_, step, ema.update) of
+ * TrainerDiffusion.  Each entry works on ALL tensors of a model, f32 and contiguous on one device, in
+ * one launch per 40 tensors; the tensor table travels in the launches' arguments, so the host arrays
+ * are read before the call returns, nothing is kept between calls and no call synchronises.
+ *
+ * sd_optim_grad_norm: total_norm = sqrt(sum of g^2 over all tensors) as clip_grad_norm_(norm_type 2,
+ *   error_if_nonfinite=False) defines it, summed in float64 through per-chunk partial sums in
+ *   `workspace` (>= sd_optim_workspace_bytes(numel, n_tensors)) in a fixed order, and
+ *   coef = min(max_norm / (total_norm + 1e-6), 1), NaN kept.  norm_coef (device, 2 floats) receives
+ *   { total_norm, coef }.  The gradients are not changed.
+ * sd_optim_adam_step: per element, in f32:  g = g coef (coef: device scalar, NULL = 1);
+ *   Adam: g' = g + wd p;  AdamW (SD_OPTIM_DECOUPLED_WD): p = p (1 - lr wd), g' = g;
+ *   m = beta1 m + (1 - beta1) g';  v = beta2 v + (1 - beta2) g'^2;  SD_OPTIM_AMSGRAD: vmax = max(vmax, v);
+ *   p = p - lr / (1 - beta1^step) * m / (sqrt(v or vmax) / sqrt(1 - beta2^step) + eps).
+ *   `step` is the tensor's own count including this step (>= 1).  With SD_OPTIM_STORE_GRADS the
+ *   clipped g is written back to grad (what clip_grad_norm_ leaves there); without it grad is only read.
+ * sd_optim_ema_update: ema[i] = lerp(ema[i], params[i], weight) in torch.lerp's two-sided form
+ *   (weight = 1 is an exact copy), 0 <= weight <= 1.
+ * Checked on the host before any device call (SD_E_INVALID names the argument): NULL arrays and NULL
+ * tensors, numel < 0, lr < 0, weight_decay < 0, step < 1, beta1 / beta2 outside [0, 1), eps < 0,
+ * max_norm <= 0, a short workspace.  n_tensors == 0 and tensors of no elements: SD_OK, nothing done. */
+#define SD_OPTIM_AMSGRAD 1
+#define SD_OPTIM_DECOUPLED_WD 2
+#define SD_OPTIM_STORE_GRADS 4
+typedef struct sd_optim_param {
+    float* p;              /* (numel) parameter, updated in place */
+    float* grad;           /* (numel) gradient */
+    float* exp_avg;        /* (numel) m */
+    float* exp_avg_sq;     /* (numel) v */
+    float* max_exp_avg_sq; /* (numel) vmax; read only with SD_OPTIM_AMSGRAD (else may be NULL) */
+    int64_t numel;
+    int64_t step;
+    double lr;
+    double weight_decay;
+} sd_optim_param;
+size_t sd_optim_workspace_bytes(const int64_t* numel, int32_t n_tensors);
+int sd_optim_grad_norm(const float* const* grads, const int64_t* numel, int32_t n_tensors, float max_norm,
+                       float* norm_coef, void* workspace, size_t workspace_bytes, void* stream);
+int sd_optim_adam_step(const sd_optim_param* params, int32_t n_tensors, double beta1, double beta2, double eps,
+                       int32_t flags, const float* coef, void* stream);
+int sd_optim_ema_update(float* const* ema, const float* const* params, const int64_t* numel, int32_t n_tensors,
+                        float weight, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,7 @@ EXPORTED = (
     "sd_cdist", "sd_set_mean_distance",
     "sd_gru_train_workspace_bytes", "sd_gru_train_forward", "sd_gru_train_backward", "sd_gx_table_forward",
     "sd_gx_table_backward",
+    "sd_optim_workspace_bytes", "sd_optim_grad_norm", "sd_optim_adam_step", "sd_optim_ema_update",
 )
 
 # sd_plan_set_option keys (include/skeldiff.h)
@@ -97,6 +98,16 @@ class SDFidClassifierDesc(ctypes.Structure):
                [(n, ctypes.c_void_p) for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0",
                                                "weight_ih_l1", "weight_hh_l1", "bias_ih_l1", "bias_hh_l1",
                                                "linear1_weight", "linear1_bias")]
+
+
+class SDOptimParam(ctypes.Structure):
+    """mirrors struct sd_optim_param (include/skeldiff.h)"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("p", "grad", "exp_avg", "exp_avg_sq", "max_exp_avg_sq")] + \
+               [("numel", ctypes.c_int64), ("step", ctypes.c_int64), ("lr", ctypes.c_double),
+                ("weight_decay", ctypes.c_double)]
+
+
+SD_OPTIM_AMSGRAD, SD_OPTIM_DECOUPLED_WD, SD_OPTIM_STORE_GRADS = 1, 2, 4
 
 
 class SkelDiffError(RuntimeError):
@@ -191,6 +202,10 @@ def _declare(lib: ctypes.CDLL) -> None:
         "sd_fid_stats_update": (ctypes.c_int, [vp, i64, i32, vp, vp, sz, vp]),
         "sd_cdist": (ctypes.c_int, [vp, i64, vp, i64, i64, vp, vp]),
         "sd_set_mean_distance": (ctypes.c_int, [vp, i64, vp, vp, i64, vp, vp]),
+        "sd_optim_workspace_bytes": (sz, [vp, i32]),
+        "sd_optim_grad_norm": (ctypes.c_int, [vp, vp, i32, ctypes.c_float, vp, vp, sz, vp]),
+        "sd_optim_adam_step": (ctypes.c_int, [vp, i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, i32, vp, vp]),
+        "sd_optim_ema_update": (ctypes.c_int, [vp, vp, vp, i32, ctypes.c_float, vp]),
         "sd_profile_step": (ctypes.c_int, [vp, vp, vp, i64, i32, i64, vp, sz, i32, ctypes.POINTER(ctypes.c_float),
                                            ctypes.POINTER(ctypes.c_int32), vp]),
     }

@@ -5,8 +5,11 @@ with the GRUs on the HIP sequence path and, in the same process on the same GPU,
 training.set_hip_training(False) (the unrolled torch ops).  Per setting: warm-up steps, then the
 median of `--reps` individually synchronised steps.  Also splits the decoder-shaped core call into
 its phases (forward sweep, reverse sweep, batched gradients) by timing the entries directly.
-Writes profiles/ae_train/bench.json and prints it.
-Usage: python tools/bench_train_autoencoder.py [--reps 9] [--warmup 3] [--out profiles/ae_train/bench.json]"""
+Writes profiles/ae_train/bench.json and prints it.  --optimizer hip runs the tail of the step as
+optim.FusedAdam(max_grad_norm=1) (DESIGN.md §4s) instead of clip_grad_norm_ + torch.optim.AdamW;
+"torch,hip" times both in the one process (the result then carries a row per optimizer).
+Usage: python tools/bench_train_autoencoder.py [--reps 9] [--warmup 3] [--out profiles/ae_train/bench.json]
+       [--optimizer torch] [--shapes 16:10,16:50,...]"""
 import argparse
 import ctypes
 import json
@@ -20,7 +23,7 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
-from skeletondiffusion_amd import _lib, synthetic, training  # noqa: E402
+from skeletondiffusion_amd import _lib, optim, synthetic, training  # noqa: E402
 from skeletondiffusion_amd.core.network.autoencoder import AutoEncoder  # noqa: E402
 from skeletondiffusion_amd.skeletons import skeleton  # noqa: E402
 
@@ -49,11 +52,13 @@ def median_ms(fn, warmup, reps):
     return statistics.median(ts), min(ts), max(ts)
 
 
-def step_time(J, B, T_obs, ph, hip, warmup, reps, dev):
+def step_time(J, B, T_obs, ph, hip, warmup, reps, dev, optimizer="torch"):
     prev = training.set_hip_training(hip)
     try:
         m = model(J, dev)
-        opt = torch.optim.AdamW(m.parameters(), lr=1e-4, amsgrad=True)
+        fused = optimizer == "hip"
+        opt = optim.FusedAdam(m.parameters(), lr=1e-4, weight_decay=1e-2, amsgrad=True, decoupled_weight_decay=True,
+                              max_grad_norm=1.0) if fused else torch.optim.AdamW(m.parameters(), lr=1e-4, amsgrad=True)
         past = torch.from_numpy(synthetic.normal((B, T_obs, J, 3), seed=51)).to(dev) * 0.3
         y = torch.from_numpy(synthetic.normal((B, ph, J, 3), seed=52)).to(dev) * 0.3
 
@@ -62,7 +67,8 @@ def step_time(J, B, T_obs, ph, hip, warmup, reps, dev):
             out, _, _ = m.autoencode(y, past, ph)
             loss = m.loss(out, y)
             loss.backward()
-            torch.nn.utils.clip_grad_norm_(m.parameters(), 1.0)
+            if not fused:
+                torch.nn.utils.clip_grad_norm_(m.parameters(), 1.0)
             opt.step()
 
         med, lo, hi = median_ms(step, warmup, reps)
@@ -116,17 +122,21 @@ def main():
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "ae_train", "bench.json"))
+    ap.add_argument("--optimizer", default="torch", help="torch, hip, or torch,hip")
+    ap.add_argument("--shapes", default="16:10,16:50,16:100,21:10,21:50,21:100", help="J:ph,...")
     a = ap.parse_args()
     assert a.reps >= 7
+    optimizers = a.optimizer.split(",")
+    assert all(o in ("torch", "hip") for o in optimizers), a.optimizer
     dev = torch.device("cuda:0")
     B, T_obs = 64, 25
     rows = []
-    for J in (16, 21):
-        for ph in (10, 50, 100):
-            hip = step_time(J, B, T_obs, ph, True, a.warmup, a.reps, dev)
-            tor = step_time(J, B, T_obs, ph, False, a.warmup, a.reps, dev)
-            rows.append({"J": J, "B": B, "T_obs": T_obs, "ph": ph, "hip": hip, "torch_ops_same_gpu": tor,
-                         "speedup": tor["median_ms"] / hip["median_ms"],
+    for J, ph in (tuple(int(v) for v in sh.split(":")) for sh in a.shapes.split(",")):
+        for optimizer in optimizers:
+            hip = step_time(J, B, T_obs, ph, True, a.warmup, a.reps, dev, optimizer)
+            tor = step_time(J, B, T_obs, ph, False, a.warmup, a.reps, dev, optimizer)
+            rows.append({"J": J, "B": B, "T_obs": T_obs, "ph": ph, "optimizer": optimizer, "hip": hip,
+                         "torch_ops_same_gpu": tor, "speedup": tor["median_ms"] / hip["median_ms"],
                          "decoder_core_phases": core_phases(J, B, ph, a.warmup, a.reps, dev)})
             print(json.dumps(rows[-1]), flush=True)
     res = {"metric": "stage-1 autoencoder training step, ms (autoencode + L1 + backward + clip_grad_norm_ + AdamW amsgrad)",
