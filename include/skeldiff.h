@@ -469,7 +469,10 @@ int sd_plan_get_option(const sd_plan* plan, int32_t option, int64_t* value);
  *           rnn.layers.0 (G_add may be NULL: no additive influence)
  *   fc_*    fc: G (J,J), weight (types, F, H), bias (types, F) or NULL
  * x (rows, 2, J, F) = the last two observed frames (x[:, -2:]), h (rows, J, L) = the sampled
- * latents -> out (rows, ph, J, F).  F <= 16, L and H multiples of 16. */
+ * latents -> out (rows, ph, J, F).  1 <= J <= 64, 1 <= F <= 16, L and H positive multiples of 16,
+ * and the gate kernel's per-row LDS (3 J H + J^2) * 4 bytes must fit in 160 KiB (J = 64: H <= 192):
+ * sd_gru_decode / sd_gru_encode refuse anything else with SD_E_INVALID before any device work, and
+ * the *_workspace_bytes functions return 0 for it (sd_last_error() names the field). */
 typedef struct sd_gru_decoder_desc {
     int32_t num_nodes, feature_size, latent_size, hidden_size, num_node_types;
     const int64_t* node_types; /* host array[J] (ignored when num_node_types == 0) */

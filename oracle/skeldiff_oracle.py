@@ -679,20 +679,34 @@ def _l1_rows(G: torch.Tensor) -> torch.Tensor:
     return G / G.abs().sum(1, keepdim=True).clamp_min(1e-12)
 
 
+def _typed(w: torch.Tensor, types, per_node_dim: int) -> torch.Tensor:
+    """Per-node weights (J, ...) of a typed tensor (types, ...); a shared one (node_types=None:
+    2-D weight, 1-D bias) is returned as it is and broadcasts over the nodes."""
+    if types is None:
+        assert w.dim() == per_node_dim, "node_types=None needs shared (2-D weight, 1-D bias) tensors"
+        return w
+    return w[types]
+
+
+def _wx(sd, key, x, types):
+    """W[type(n)] x[b, n] for x (B, J, D) -> (B, J, O)."""
+    W = _typed(sd[key].double(), types, 2)
+    return torch.einsum("nod,bnd->bno", W, x) if W.dim() == 3 else x @ W.transpose(-2, -1)
+
+
 def _sgl(sd, pre, x, types):
     """StaticGraphLinear with learn_influence (graph_structural.py:30-43): Ghat (W[type] x + b)."""
-    W = sd[pre + "weight"].double()[types]
-    y = torch.einsum("nod,bnd->bno", W, x)
+    y = _wx(sd, pre + "weight", x, types)
     if pre + "bias" in sd:
-        y = y + sd[pre + "bias"].double()[types]
+        y = y + _typed(sd[pre + "bias"].double(), types, 1)
     return _l1_rows(sd[pre + "G"].double()) @ y
 
 
 def _gru_cell(sd, pre, x, hx, gx, types, additive: bool):
     """recurrent.py:321-366 (clockwork off): one step, returns (hy, next gx)."""
     H = hx.shape[-1]
-    xr = gx @ (torch.einsum("nod,bnd->bno", sd[pre + "weight_ih"].double()[types], x) + sd[pre + "bias_ih"].double()[types])
-    hr = gx @ (torch.einsum("nod,bnd->bno", sd[pre + "weight_hh"].double()[types], hx) + sd[pre + "bias_hh"].double()[types])
+    xr = gx @ (_wx(sd, pre + "weight_ih", x, types) + _typed(sd[pre + "bias_ih"].double(), types, 1))
+    hr = gx @ (_wx(sd, pre + "weight_hh", hx, types) + _typed(sd[pre + "bias_hh"].double(), types, 1))
     r = torch.sigmoid(xr[..., :H] + hr[..., :H])
     z = torch.sigmoid(xr[..., H:2 * H] + hr[..., H:2 * H])
     n = torch.tanh(xr[..., 2 * H:] + r * hr[..., 2 * H:])
@@ -701,10 +715,15 @@ def _gru_cell(sd, pre, x, hx, gx, types, additive: bool):
     return hy, _l1_rows(g)
 
 
+def _types(node_types):
+    return None if node_types is None else torch.as_tensor(node_types, dtype=torch.long)
+
+
 def gru_decode(sd, node_types, x2, h, ph, prefix="decoder."):
     """AutoEncoder.decode -> Decoder.forward (decoder.py:60-104): x2 (B, 2, J, F) the last two
-    observed frames, h (B, J, L) the latent -> (B, ph, J, F)."""
-    types = torch.as_tensor(node_types, dtype=torch.long)
+    observed frames, h (B, J, L) the latent -> (B, ph, J, F).  node_types=None: a module built
+    without node types (one shared 2-D weight and 1-D bias for every node)."""
+    types = _types(node_types)
     x2, h = x2.double(), h.double()
     hx = _sgl(sd, prefix + "initial_hidden_h.", torch.cat([x2[:, 0], h], -1), types)
     rec = torch.cat([x2[:, 1], h], -1)
@@ -717,8 +736,9 @@ def gru_decode(sd, node_types, x2, h, ph, prefix="decoder."):
 
 
 def gru_encode(sd, node_types, x, prefix="encoder."):
-    """Encoder.forward (encoder.py:75-80) + z_activation tanh (autoencoder.py:47-51): x (B, T, J, F)."""
-    types = torch.as_tensor(node_types, dtype=torch.long)
+    """Encoder.forward (encoder.py:75-80) + z_activation tanh (autoencoder.py:47-51): x (B, T, J, F);
+    node_types=None as in gru_decode."""
+    types = _types(node_types)
     x = x.double()
     hx = _sgl(sd, prefix + "initial_hidden1.", x[:, 0], types)
     gx = _l1_rows(sd[prefix + "rnn.layers.0.G"].double())

@@ -10,8 +10,11 @@
 //   hx <- n - n z + z hx                                -> k_gru_gate (mixes x_res on the fly)
 //   out[:, t] = tanh(Ghat_fc (W_fc[type] hx + b_fc))    -> graph-linear launch, tanh epilogue
 //   hx_0 = Ghat_init (W_init[type] [x_prev | h] + b_init)
-// The graph linears run on the exact-f32 kernels (row-major); the 3-feature frame inputs are
-// zero-padded to 16 so K stays a multiple of 16.
+// The graph linears run on the exact-f32 kernels (row-major; no split-f16 weights are prepared, so
+// launch_graph_linear never takes a v4 route): v3 at J = 16 / 17 / 21 with N < 512, v5 (k_gl5_gemm,
+// then k_gl5_mix or, where N % 64 == 0, the f32-MFMA k_gl5_mixd) at J > 21, the v2 tiles otherwise.
+// The F <= 16 frame features are zero-padded to 16 so K stays a multiple of 16.
+// (tests/test_gpu_decoder_shapes.py runs each of these routes from the decoder and the encoder.)
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -25,6 +28,7 @@ namespace sd {
 namespace {
 
 constexpr int KF = 16;  // padded width of the frame features (F <= 16)
+constexpr size_t kGateLdsMax = 160 * 1024;  // k_gru_gate's dynamic LDS (gl3_launch / gl2_launch use the same limit)
 
 // gx table: row i of gx_t for t = 0 .. ph-1 (rows are independent under the row-L1 normalize)
 __global__ void k_gx_table(const float* __restrict__ G, const float* __restrict__ Gadd, int J, int ph,
@@ -194,8 +198,22 @@ int check_desc(const sd_gru_decoder_desc* d) {
         for (int j = 0; j < d->num_nodes; ++j)
             if (d->node_types[j] < 0 || d->node_types[j] >= d->num_node_types)
                 return dfail(SD_E_INVALID, "node_types out of range");
-    if (!d->init_G || !d->init_weight || !d->G || !d->weight_ih || !d->weight_hh || !d->fc_G || !d->fc_weight)
-        return dfail(SD_E_INVALID, "null decoder tensor");
+    const struct {
+        const float* p;
+        const char* name;
+    } need[] = {{d->init_G, "init_G"},       {d->init_weight, "init_weight"}, {d->G, "G"},
+                {d->weight_ih, "weight_ih"}, {d->weight_hh, "weight_hh"},     {d->fc_G, "fc_G"},
+                {d->fc_weight, "fc_weight"}};
+    for (const auto& t : need)
+        if (!t.p) return dfail(SD_E_INVALID, std::string("null decoder tensor: ") + t.name);
+    // k_gru_gate keeps a row's x_res (J, 3H) and gx_t (J, J) in dynamic LDS: refuse what cannot fit
+    // (160 KiB, the limit of the graph-linear launches) here, not mid-sequence as an SD_E_HIP
+    const size_t gate_lds = ((size_t)d->num_nodes * 3 * d->hidden_size + (size_t)d->num_nodes * d->num_nodes) * sizeof(float);
+    if (gate_lds > sd::kGateLdsMax)
+        return dfail(SD_E_INVALID, "num_nodes = " + std::to_string(d->num_nodes) + " with hidden_size = " +
+                                       std::to_string(d->hidden_size) + " needs " + std::to_string(gate_lds) +
+                                       " bytes of gate LDS (3 num_nodes hidden_size + num_nodes^2 floats), over the " +
+                                       std::to_string(sd::kGateLdsMax) + " available");
     return SD_OK;
 }
 }  // namespace
@@ -203,7 +221,11 @@ int check_desc(const sd_gru_decoder_desc* d) {
 extern "C" {
 
 size_t sd_gru_decode_workspace_bytes(const sd_gru_decoder_desc* d, int64_t rows, int32_t ph) {
-    if (check_desc(d) || rows < 0 || ph < 1) return 0;
+    if (check_desc(d)) return 0;
+    if (rows < 0 || ph < 1) {
+        dfail(SD_E_INVALID, "rows >= 0 and ph >= 1 required");
+        return 0;
+    }
     return sd::carve(d, rows, ph, nullptr, nullptr) + 256;
 }
 
@@ -216,8 +238,9 @@ int sd_gru_decode(const sd_gru_decoder_desc* d, const float* x, const float* h, 
     if (!x || !h || !out) return dfail(SD_E_INVALID, "null input / output");
     const size_t need = sd::carve(d, rows, ph, nullptr, nullptr);
     char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    if (!workspace || (size_t)(base - (char*)workspace) + need > ws_bytes)
-        return dfail(SD_E_INVALID, "workspace too small: need " + std::to_string(need + 256));
+    // the size *_workspace_bytes reports (256 spare bytes cover the alignment of any pointer)
+    if (!workspace || ws_bytes < need + 256)
+        return dfail(SD_E_INVALID, "workspace missing or too small: need " + std::to_string(need + 256) + " bytes");
     sd::DecWS w;
     sd::carve(d, rows, ph, base, &w);
     hipStream_t s = (hipStream_t)stream;
@@ -265,7 +288,11 @@ int sd_gru_decode(const sd_gru_decoder_desc* d, const float* x, const float* h, 
 }
 
 size_t sd_gru_encode_workspace_bytes(const sd_gru_decoder_desc* d, int64_t rows, int32_t frames) {
-    if (check_desc(d) || rows < 0 || frames < 1) return 0;
+    if (check_desc(d)) return 0;
+    if (rows < 0 || frames < 1) {
+        dfail(SD_E_INVALID, "rows >= 0 and frames >= 1 required");
+        return 0;
+    }
     return sd::carve(d, rows, frames, nullptr, nullptr) + 256;
 }
 
@@ -283,8 +310,9 @@ int sd_gru_encode(const sd_gru_decoder_desc* d, const float* x, int64_t rows, in
     if (d->G_add) return dfail(SD_E_INVALID, "the encoder GRU has no additive graph influence (G_add must be NULL)");
     const size_t need = sd::carve(d, rows, frames, nullptr, nullptr);
     char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    if (!workspace || (size_t)(base - (char*)workspace) + need > ws_bytes)
-        return dfail(SD_E_INVALID, "workspace too small: need " + std::to_string(need + 256));
+    // the size *_workspace_bytes reports (256 spare bytes cover the alignment of any pointer)
+    if (!workspace || ws_bytes < need + 256)
+        return dfail(SD_E_INVALID, "workspace missing or too small: need " + std::to_string(need + 256) + " bytes");
     sd::DecWS w;
     sd::carve(d, rows, frames, base, &w);
     hipStream_t s = (hipStream_t)stream;

@@ -1,7 +1,8 @@
 """Graph-GRU autoencoder against the reference's own AutoEncoder outputs
 (tests/golden/decoder.npz, gen_golden.py:gen_decoder): the oracle restatement and the mirrored
 modules on CPU, the HIP decoder (sd_gru_decode) on the GPU.  Tolerance 1e-4 on the decoded
-frames (fp32; 120 recurrent steps)."""
+frames (fp32; 120 recurrent steps).  Other skeletons, sizes, routes and edges at a measured
+tolerance: tests/test_gpu_decoder_shapes.py; argument validation: tests/test_decoder_host.py."""
 import numpy as np
 import pytest
 import torch
