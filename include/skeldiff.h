@@ -657,6 +657,53 @@ int sd_optim_adam_step(const sd_optim_param* params, int32_t n_tensors, double b
 int sd_optim_ema_update(float* const* ema, const float* const* params, const int64_t* numel, int32_t n_tensors,
                         float weight, void* stream);
 
+/* Motion batches from clips resident on the device: the reference's per-item data path for a
+ * whole batch in one kernel.  It replaces BaseDataset.__getitem__ / _get_segment
+ * (src/data/loaders/base/base_dataset.py:109-133, :164-177), add_noise and MotionDataset.__getitem__ /
+ * data_augmentation / tranform2inputspace (src/data/loaders/base/motion_dataset.py:11-19, :129-165, :176-193),
+ * Skeleton.tranform_to_input_space with if_consider_hip = False (src/data/skeleton/motion/base.py:35-42,
+ * centerpose.py:13-18, rescalepose.py:17-25, utils.py:3-8), default_collate and the host-to-device copy.
+ * sd_motion_batch, per sample b (every step in f32, one rounding per operation):
+ *   segment = clamp(stride * sample_idx[b] + augmentation (+ offset in [-augmentation, augmentation] when
+ *   augmentation != 0), 0, nseg - 1); its obs_len + pred_len frames start at global frame seg_first[segment] of
+ *   frames (total_frames, joints, 3); segment_idx[b] = segment.
+ *   noisy: joints 1.. of the observation frames: a (frame, joint) pair is hit with probability noise_level and
+ *   gets noise_std * a normal per coordinate; in eval mode too, before the augmentation.
+ *   train: coordinate m in (0, 1) changes sign with probability da_mirroring each; with probability
+ *   da_rotations an integer angle d in [0, 360): x' = c x - s y, y' = s x + c y, c = rot_table[d],
+ *   s = rot_table[360 + d] (DEVICE, 720 floats: the f32 roundings of the f64 cosines, then sines).
+ *   representation: SD_MOTION_RESCALE_POSE subtracts joint 0 of the same frame and divides by pose_box_size
+ *   (a correctly rounded division); SD_MOTION_CENTER_POSE subtracts only; SD_MOTION_VANILLA neither.  Joint 0
+ *   is dropped: obs (B, obs_len, joints - 1, 3), pred (B, pred_len, joints - 1, 3).
+ *   Draws: with every draw_* pointer NULL they come from the sampler's Philox stream (sd_philox_raw) keyed
+ *   (seed, row = sample_idx[b], step = epoch) -- the quad map is in csrc/sd_motion_batch_addr.h --, so a
+ *   sample's draws do not depend on its batch.  Otherwise draw_offset (B) i32, draw_mirror (B, 2) u8 and
+ *   draw_degrees (B) i32 (-1: no rotation) are read instead, and with noisy draw_noise_mask (B, obs_len,
+ *   joints - 1) u8 and draw_noise (B, obs_len, joints - 1, 3) f32 (already times noise_std).
+ * sd_motion_draws writes the Philox stream's decisions in exactly that form (noise_mask and noise both NULL:
+ *   the per-sample ones only); sd_motion_batch given them returns the bits of its Philox path.
+ * sd_motion_batch_frame_tile: frames per workgroup for a joint count (-1 outside [2, 64]).
+ * All pointers are DEVICE memory; frames is only read (the resident clips are never written).  Checked on the
+ * host before any device call (SD_E_INVALID names the argument): NULL pointers, joints outside [2, 64],
+ * obs_len / pred_len < 1, nseg < 1, total_frames < obs_len + pred_len, stride < 1, augmentation < 0,
+ * pose_box_size <= 0, probabilities outside [0, 1], noise_std < 0, an unknown representation.  B == 0: SD_OK,
+ * nothing launched.  sample_idx cannot be checked on the host: the kernel clamps the segment as above. */
+#define SD_MOTION_VANILLA 0
+#define SD_MOTION_CENTER_POSE 1
+#define SD_MOTION_RESCALE_POSE 2
+int sd_motion_batch(const float* frames, int64_t total_frames, const int64_t* seg_first, int64_t nseg,
+                    const int64_t* sample_idx, int64_t B, int32_t joints, int32_t obs_len, int32_t pred_len,
+                    int64_t stride, int64_t augmentation, int32_t train, int32_t representation, float pose_box_size,
+                    float da_mirroring, float da_rotations, int32_t noisy, float noise_level, float noise_std,
+                    const float* rot_table, uint64_t seed, int32_t epoch, const int32_t* draw_offset,
+                    const uint8_t* draw_mirror, const int32_t* draw_degrees, const uint8_t* draw_noise_mask,
+                    const float* draw_noise, float* obs, float* pred, int64_t* segment_idx, void* stream);
+int sd_motion_draws(const int64_t* sample_idx, int64_t B, int32_t joints, int32_t obs_len, int64_t augmentation,
+                    float da_mirroring, float da_rotations, float noise_level, float noise_std, uint64_t seed,
+                    int32_t epoch, int32_t* offset, uint8_t* mirror, int32_t* degrees, uint8_t* noise_mask, float* noise,
+                    void* stream);
+int32_t sd_motion_batch_frame_tile(int32_t joints);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,6 +47,7 @@ EXPORTED = (
     "sd_gru_train_workspace_bytes", "sd_gru_train_forward", "sd_gru_train_backward", "sd_gx_table_forward",
     "sd_gx_table_backward",
     "sd_optim_workspace_bytes", "sd_optim_grad_norm", "sd_optim_adam_step", "sd_optim_ema_update",
+    "sd_motion_batch", "sd_motion_draws", "sd_motion_batch_frame_tile",
 )
 
 # sd_plan_set_option keys (include/skeldiff.h)
@@ -108,6 +109,7 @@ class SDOptimParam(ctypes.Structure):
 
 
 SD_OPTIM_AMSGRAD, SD_OPTIM_DECOUPLED_WD, SD_OPTIM_STORE_GRADS = 1, 2, 4
+SD_MOTION_VANILLA, SD_MOTION_CENTER_POSE, SD_MOTION_RESCALE_POSE = 0, 1, 2
 
 
 class SkelDiffError(RuntimeError):
@@ -206,6 +208,12 @@ def _declare(lib: ctypes.CDLL) -> None:
         "sd_optim_grad_norm": (ctypes.c_int, [vp, vp, i32, ctypes.c_float, vp, vp, sz, vp]),
         "sd_optim_adam_step": (ctypes.c_int, [vp, i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, i32, vp, vp]),
         "sd_optim_ema_update": (ctypes.c_int, [vp, vp, vp, i32, ctypes.c_float, vp]),
+        "sd_motion_batch": (ctypes.c_int, [vp, i64, vp, i64, vp, i64, i32, i32, i32, i64, i64, i32, i32, ctypes.c_float,
+                                           ctypes.c_float, ctypes.c_float, i32, ctypes.c_float, ctypes.c_float, vp, u64, i32,
+                                           vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "sd_motion_draws": (ctypes.c_int, [vp, i64, i32, i32, i64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                           ctypes.c_float, u64, i32, vp, vp, vp, vp, vp, vp]),
+        "sd_motion_batch_frame_tile": (i32, [i32]),
         "sd_profile_step": (ctypes.c_int, [vp, vp, vp, i64, i32, i64, vp, sz, i32, ctypes.POINTER(ctypes.c_float),
                                            ctypes.POINTER(ctypes.c_int32), vp]),
     }
