@@ -418,7 +418,7 @@ enum {
     SD_OPT_KERNEL_VARIANT = 1,  /* 0 auto, 1..5 force a graph-linear generation */
     SD_OPT_GL4_TILE = 2,        /* v4 tile <waves><row tiles><col tiles>, 0 = per shape */
     SD_OPT_ROW_CHAINS = 3,      /* 1..8 concurrent row chains in sd_sample_loop; 0 = auto
-                                   (3, or 2 at <= SKELDIFF_SPLIT_ROWS rows) */
+                                   (3, or 2 at <= 1,200 rows) */
     SD_OPT_PRECISION = 4,       /* as sd_plan_set_precision */
     SD_OPT_GL4_STAGING = 5,     /* v4 weight stages: 0 LDS-DMA (default), 1 register-staged;
                                    2 = 0 (a round-2 diagnostic setting, kept for compatibility) */
@@ -434,7 +434,7 @@ enum {
     SD_OPT_LAST_CHAINS = 7,     /* read-only: row chains the plan's last sd_sample_loop ran (the
                                    SD_OPT_ROW_CHAINS value, fewer for batches of fewer than n
                                    32-row units, a ragged last unit counting; auto: 1 at <= 128
-                                   rows, 2 at <= SKELDIFF_SPLIT_ROWS, else 3); 0 before the first
+                                   rows, 2 at <= 1,200 rows, else 3); 0 before the first
                                    call */
     SD_OPT_LAST_ROUTE = 8,      /* read-only: kernels the plan's last sd_sample_loop launched, bits
                                    1 one-kernel k_gl4, 2 fused to_qkv + attention k_gl4, 4 k_gl4y

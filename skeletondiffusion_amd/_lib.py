@@ -12,7 +12,7 @@ import threading
 from typing import Optional
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# SKELDIFF_LIB: load another build of the library (e.g. the libskeldiff_dbg.so diagnostic variant)
+# SKELDIFF_LIB: load another build of the library (e.g. a tagged variant of build_library(extra=...))
 LIB_PATH = os.environ.get("SKELDIFF_LIB") or os.path.join(HERE, "libskeldiff.so")
 
 # include/skeldiff.h SD_ABI_VERSION: a library of another ABI is refused at load (round 4 changed

@@ -47,20 +47,20 @@ DEVICE_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 _FEATURE_NOTE = b"'-packed-fp32-ops' is not a recognized feature for this target"
 
 
-def build_library(force: bool = False, verbose: bool = False, debug_lds: bool = False, extra=(), tag="_dbg",
+def build_library(force: bool = False, verbose: bool = False, extra=(), tag="_dbg",
                   packed_fp32: bool = False) -> str:
-    """debug_lds: the diagnostic variant libskeldiff_dbg.so (-DSD_DEBUG_LDS: LDS integrity
-    counters in k_gl4 / k_update, sd_debug_lds_counters); load it with SKELDIFF_LIB.
+    """extra: more hipcc flags, which make a tagged diagnostic variant (libskeldiff{tag}.so); load
+    it with SKELDIFF_LIB.
     packed_fp32: the round-3 hazard reproduction build, always a tagged
     diagnostic variant (libskeldiff_packed.so unless `tag` says otherwise).
     Every product build is checked after linking (isa_check: gfx950 code objects only, no
     packed-FP32 instruction) and stamped with its flags."""
-    variant = debug_lds or bool(extra) or packed_fp32  # a diagnostic variant: libskeldiff{tag}.so, never the product
+    variant = bool(extra) or packed_fp32  # a diagnostic variant: libskeldiff{tag}.so, never the product
     if packed_fp32 and tag == "_dbg":
         tag = "_packed"
     out = OUT.replace(".so", tag + ".so") if variant else OUT
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-failed"] + \
-        ([] if packed_fp32 else DEVICE_FLAGS) + (["-DSD_DEBUG_LDS"] if debug_lds else []) + list(extra)
+        ([] if packed_fp32 else DEVICE_FLAGS) + list(extra)
     stamp = " ".join(flags)
     if not force and not variant and not _stale(stamp):
         return OUT
@@ -105,4 +105,4 @@ def build_library(force: bool = False, verbose: bool = False, debug_lds: bool = 
 
 
 if __name__ == "__main__":
-    print(build_library(force=True, verbose=True, debug_lds="--debug-lds" in sys.argv))
+    print(build_library(force=True, verbose=True))

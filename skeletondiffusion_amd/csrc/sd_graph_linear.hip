@@ -16,7 +16,6 @@
 // next fill overwrites (WAR).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "sd_internal.h"
 
@@ -261,13 +260,7 @@ static hipError_t gl2_launch(const GLArgs& a, bool rms, hipStream_t s) {
 
 // Column-tile width: 32 (NCB=2) halves the x re-reads, 16 (NCB=1) doubles the number of
 // workgroups; at small B*N the 32-wide grid cannot give every CU two workgroups, so go narrow.
-// SKELDIFF_GL_NCB=1|2 forces a width (tuning / A-B runs).
 static int ncb_choice(const GLArgs& a) {
-    static const int forced = [] {
-        const char* e = getenv("SKELDIFF_GL_NCB");
-        return e ? atoi(e) : 0;
-    }();
-    if (forced == 1 || forced == 2) return forced;
     const int64_t wgs32 = (int64_t)((a.N + 31) / 32) * ((a.B + 63) / 64);
     return wgs32 >= 2 * 256 ? 2 : 1;
 }

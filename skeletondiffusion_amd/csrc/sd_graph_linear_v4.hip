@@ -25,7 +25,6 @@
 //     G-hat mixing on 16x16x4 f32 MFMA, FiLM / tanh / residual / store.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include <algorithm>
 #include <cmath>
@@ -1179,26 +1178,6 @@ __device__ __forceinline__ void gl4_body(const GLArgs& p, const int bx, const in
             __builtin_amdgcn_global_load_lds((const void*)src, (lds_void*)(dst + (size_t)q0 * 8), 16, 0, 0);
         }
     };
-#ifdef SD_DEBUG_LDS
-    // stage c against its global source, read in the phase that reads the stage anyway
-    auto check_stage = [&](int c) {
-        constexpr int PPT = TILE_H / 8;
-        const int per_type = CT * PPT;
-        const int npieces = p.ntypes * per_type;
-        const _Float16* st = (c & 1) ? sW1 : sW0;
-        unsigned bad = 0;
-        for (int q = tid; q < npieces; q += NTH) {
-            const int t = q / per_type, rem = q - t * per_type;
-            const int ct = rem / PPT;
-            const int tile = MODE == 1 ? ctile + ct * p.attn_heads : (c0 >> 5) + ct;
-            const uint4 g = *reinterpret_cast<const uint4*>(p.wsp + (((int64_t)t * nchunk + c) * p.wsp_nct + tile) * 1024 +
-                                                            (rem % PPT) * 8);
-            const uint4 l = *reinterpret_cast<const uint4*>(st + (size_t)q * 8);
-            bad += (g.x != l.x) + (g.y != l.y) + (g.z != l.z) + (g.w != l.w);
-        }
-        if (bad) atomicAdd(&p.dbg[0], bad);
-    };
-#endif
     auto compute = [&](int c, const XBuf& xb) {
         const _Float16* cur = (c & 1) ? sW1 : sW0;
         const bool rms_chunk = RMS && (c << 4) < p.K1;
@@ -1279,9 +1258,6 @@ __device__ __forceinline__ void gl4_body(const GLArgs& p, const int bx, const in
             load_x(c + 1, nxt);
         }
         compute(c, cur);
-#if defined(SD_DEBUG_LDS) && !defined(SD_DEBUG_NO_GL)
-        check_stage(c);
-#endif
     };
 
     // G-hat and FiLM (scale + 1 | shift) for this workgroup's columns -> LDS, bias -> registers:
@@ -1408,13 +1384,6 @@ __device__ __forceinline__ void gl4_body(const GLArgs& p, const int bx, const in
         }
     }
     }  // MODE < 2: K loop
-#if defined(SD_DEBUG_LDS) && !defined(SD_DEBUG_NO_G)
-    {
-        unsigned bad = 0;
-        for (int i = tid; i < J * J; i += NTH) bad += sG[i] != p.G[i];
-        if (bad) atomicAdd(&p.dbg[2], bad);
-    }
-#endif
     if constexpr (MODE == 1) {
         attention_epilogue<J, NW, NPW>(p, acc, smem, sG, row0, ctile, wave, lane);
         return;
@@ -1543,14 +1512,7 @@ __global__ __launch_bounds__(512, 1) void k_gl4_pair(const GLArgs a, const GLArg
 }
 
 // v4 weight staging (GLArgs::gl4_stage): 0 = LDS-DMA stages, 1 = register-staged stages (2, a
-// round-2 diagnostic setting, is now the same as 0: every launch takes its exact LDS).  Process
-// default SKELDIFF_GL4_STAGE for new plans.
-static int g_gl4_stage = [] {
-    const char* e = getenv("SKELDIFF_GL4_STAGE");
-    const int v = e ? atoi(e) : 0;
-    return (v >= 0 && v <= 2) ? v : 0;
-}();
-int gl4_stage_default() { return g_gl4_stage; }
+// round-2 diagnostic setting, is now the same as 0: every launch takes its exact LDS).
 
 template <int J, int NW, int RT, int CT, int MODE = 0, int PREC = 0, int STG = 0>
 static hipError_t gl4_launch_t(const GLArgs& a, bool rms, hipStream_t s);
@@ -1592,14 +1554,6 @@ static hipError_t gl4_launch_t(const GLArgs& a, bool rms, hipStream_t s) {
     return hipGetLastError();
 }
 
-// SKELDIFF_GL4_CFG = <NW><RT><CT> (e.g. 822): process default of the plans' v4 tile (tuning);
-// 0/unset = per shape.
-static int g_gl4_cfg = [] {
-    const char* e = getenv("SKELDIFF_GL4_CFG");
-    return e ? atoi(e) : 0;
-}();
-int gl4_tile_default() { return g_gl4_cfg; }
-
 // ---- split route (small grids) -------------------------------------------------
 // A one-kernel launch is one workgroup's K-loop latency however few workgroups it has: at 50
 // rows an N = 192 layer is 12 workgroups on 256 CUs.  The split route runs phase 1 (k_gl4y, one
@@ -1608,15 +1562,7 @@ int gl4_tile_default() { return g_gl4_cfg; }
 // the attention epilogue per 8-row slab).  Same arithmetic in the same order as the one-kernel
 // route, so the results are bitwise identical and the route can follow the shard size.
 // Auto threshold on the rows of the whole sampling call (all row chains; GLArgs::route_rows):
-// process default SKELDIFF_SPLIT_ROWS = 1200.  Measured (round 4, same box, T = 100, J = 16 f32,
-// tools/sweep_routes.py, profiles/r04j/sweep.txt; k_gl4y with every chunk in flight): 800 rows
-// 9,648 futures/s (k_gl4y, 2 chains) vs 7,737 (k_gl4t, 3); 1,600 rows 12,109 vs 12,172 (equal);
-// 400 rows 6,165 vs 4,361.
-static int64_t g_split_rows = [] {
-    const char* e = getenv("SKELDIFF_SPLIT_ROWS");
-    return e ? (int64_t)atoll(e) : (int64_t)1200;
-}();
-int64_t split_rows_default() { return g_split_rows; }
+// kSplitRows (sd_internal.h).
 
 // 0: one-kernel route; 1: split route with the per-wave phase 1 (k_gl4y, small grids); 2: split
 // route with the tiled phase 1 (k_gl4t, full batches).  GLArgs::split: 0 auto, 1 never, 2 always
@@ -1637,7 +1583,7 @@ static int split_route(const GLArgs& a, bool attn) {
     if (a.split == 4) return attn ? 0 : 2;  // tiled GEMM phase; to_qkv + attention on the one-kernel tile
     if (a.gl4_cfg != 0 && !ln) return 0;
     const int64_t rows = a.route_rows > 0 ? a.route_rows : a.B;
-    if (rows <= g_split_rows) return a.prec == 2 ? (ln ? 2 : 0) : 1;
+    if (rows <= kSplitRows) return a.prec == 2 ? (ln ? 2 : 0) : 1;
     // J = 17 / 21 full batches (f32 and half; bf16 at J = 17): the tiled route on one chain measured
     // faster than the one-kernel route on three (FreeMan J = 17 10,954 vs 9,547, AMASS J = 21 8,567
     // vs 8,371 futures/s at 3,200 rows, T = 100; config 5 half 133,002 vs 92,456, bf16 134,084 vs
@@ -1741,19 +1687,12 @@ static hipError_t launch_gl4t(const GLArgs& a, bool rms, int64_t ntile_r, const 
     // f16 operands, row-blocked x, N = 96 / 192: 2 row tiles x 3 column tiles per wave (row-major x
     // -- the J > 21 path -- keeps 1 x 6: its x fragments are 16-B pieces of rows J K floats apart,
     // and a second row tile doubled them; MANO N = 192 29.1 vs 26.7 us, profiles/r06h)
-#ifndef SD_GL4T_RT2
-#define SD_GL4T_RT2 1
-#endif
-#ifndef SD_GL4T_PF
-#define SD_GL4T_PF 2  // chunks in flight of the row-blocked forms (A/B builds: -DSD_GL4T_PF=3 / 4)
-#endif
-#ifndef SD_GL4T_PF6
-#define SD_GL4T_PF6 2
-#endif
-    constexpr int PFB = ROWMAJOR ? 2 : SD_GL4T_PF, PF6 = ROWMAJOR ? 2 : SD_GL4T_PF6;
+    constexpr bool kRt2 = true;
+    constexpr int kPf = 2, kPf6 = 2;  // chunks in flight of the row-blocked forms (3 / 4 measured no faster)
+    constexpr int PFB = ROWMAJOR ? 2 : kPf, PF6 = ROWMAJOR ? 2 : kPf6;
     // a paired launch (GLArgs::pair_n) takes the form of its layers, with twice the column groups
     const int Nt = a.pair_n ? a.pair_n : a.N;
-    if (!ROWMAJOR && SD_GL4T_RT2 && a.prec != 2 && Nt <= 192 && Nt % 96 == 0) {
+    if (!ROWMAJOR && kRt2 && a.prec != 2 && Nt <= 192 && Nt % 96 == 0) {
         if (K == 192) return launch_gl4t_v<3, 12, ROWMAJOR, 2, PFB>(a, rms, ntile_r, yo, s);
         if (K == 256) return launch_gl4t_v<3, 16, ROWMAJOR, 2, PFB>(a, rms, ntile_r, yo, s);
         if (K == 384) return launch_gl4t_v<3, 24, ROWMAJOR, 2, PFB>(a, rms, ntile_r, yo, s);

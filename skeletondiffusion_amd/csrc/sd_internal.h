@@ -10,13 +10,6 @@ namespace sd {
 
 constexpr int kMaxNodes = 64;
 
-#ifdef SD_DEBUG_LDS
-// diagnostic build only (build.py debug=True): LDS integrity counters (device, 8 words) that
-// GLArgs::dbg / UpdArgs::dbg point to: [0] k_gl4 weight stages vs their global source,
-// [1] k_update tables vs global, [2] k_gl4 G-hat table
-unsigned* debug_counters();
-#endif
-
 // One StaticGraphLinear (graph_structural.py:30-43) with its fused epilogue:
 //   y_j   = s_j * (W_type(j) [x1_j | x2_j]) + bias_type(j)        (s_j = 1/max(|x1_j|,1e-12) if RMS)
 //   z_i   = sum_j Ghat[i][j] y_j
@@ -27,8 +20,8 @@ struct GLArgs {
     const float* x1; int64_t x1_rs; int K1; int x1_div;   // row b reads x1 row (b + x1_row0) / x1_div
     int64_t x1_row0;                                      // 0 <= x1_row0 < x1_div (a row chunk's phase)
     int tile_hint;                                        // v4 tile <NW><RT><CT> when gl4_cfg is 0 (0: per shape)
-    // per-launch kernel selection (the plan's options, sd_plan_set_option; process defaults for
-    // the test entry points): generation 0 auto / 1..5 forced, v4 tile <NW><RT><CT> (0 auto),
+    // per-launch kernel selection (the plan's options, sd_plan_set_option; the sd_test_set_* hooks
+    // for the test entry points): generation 0 auto / 1..5 forced, v4 tile <NW><RT><CT> (0 auto),
     // v4 weight staging 0 LDS-DMA (CU held exclusively) / 1 register-staged (CU shareable)
     int variant, gl4_cfg, gl4_stage;
     // v4 split route (phase 1 GEMM per (tile, node) into the zs scratch, phase 2 mixing epilogue;
@@ -65,7 +58,6 @@ struct GLArgs {
     // v5: scratch for the pre-mix activations when res aliases out (zs_cap floats), or null;
     // v4 split route: the pre-mix Y of phase 1
     float* zs; int64_t zs_cap;
-    unsigned* dbg;  // SD_DEBUG_LDS builds only: integrity counters (else unused)
     // v4: bit 0 set (atomicOr) when an activation is outside the f16 range of the split
     // (|x| >= 65504: x_hi would be inf); null = not checked
     unsigned* status;
@@ -85,8 +77,12 @@ struct GLArgs {
     const float* W2 = nullptr;
     float wsp_unscale2 = 1.f;
     int zs_n = 0, zs_c0 = 0;
+    // The struct is a kernel argument, and its size stays a whole number of 64-B lines: at 8 bytes
+    // less (a removed member) every launch of the small-batch routes measured about 0.3 us longer,
+    // 1.2 - 1.8 % of a 400- or 50-row step
+    int line_pad_[2] = {0, 0};
 };
-int diag_flags();  // SKELDIFF_DIAG (sd_plan.hip)
+static_assert(sizeof(GLArgs) % 64 == 0, "GLArgs: a whole number of 64-B lines (see line_pad_)");
 
 // Kernels a sampling call launched (SD_OPT_LAST_ROUTE): every graph-linear / attention launch site
 // ORs its bit into this host thread's word while run_denoiser records (eager) or captures (graph).
@@ -137,12 +133,8 @@ struct UpdArgs {
     float* out; float* out2; int64_t out2_rs;
     float* mean_out; int64_t mean_rs; float* noise_out; int64_t noise_rs;
     int64_t B; int J; int D;
-    unsigned* dbg;  // SD_DEBUG_LDS builds only
     int x0_bf16, xt_bf16, out_bf16;  // bf16 latents (precision mode 2); out2 / records stay f32
     int elementwise;  // SD_OPT_UPDATE_KERNEL: 0 k_update_mfma where it applies, 1 the element-per-thread forms
-    // diagnostics only (sd_debug_update_dump): the J values of x0 (activation + clamp applied),
-    // x_t and sigma eps each thread computed from, stored after its outputs; null = off
-    float* dump_x0; float* dump_xt; float* dump_ev;
 };
 
 hipError_t launch_graph_linear(const GLArgs& a, bool rms, hipStream_t s);     // dispatches v1..v5
@@ -154,18 +146,18 @@ hipError_t launch_graph_linear_v4(const GLArgs& a, bool rms, hipStream_t s);  //
 hipError_t launch_qkv_attention_v4(const GLArgs& a, bool rms, hipStream_t s);  // J <= 16, dh 32
 // split-f16 GEMM phase (k_gl4y) into row-major z (B, J, N) with row stride z_rs (v5, J > 21)
 hipError_t launch_gemm_split(const GLArgs& a, bool rms, float* z, int64_t z_rs, hipStream_t s);
-// process defaults that new plans (and the sd_test_* hooks) start from: SKELDIFF_GL_VARIANT
-// (0 auto, 1..5), SKELDIFF_GL4_CFG (<NW><RT><CT>, 0 auto), SKELDIFF_GL4_STAGE (0 / 1), read at load
-int graph_linear_variant();
-int gl4_tile_default();
-int gl4_stage_default();
+// Rows (of the whole sampling call, all row chains) at or below which the v4 layers take the
+// small-batch split route (k_gl4y) and an auto plan runs two row chains.  Measured (round 4, same
+// box, T = 100, J = 16 f32, tools/sweep_routes.py, profiles/r04j/sweep.txt; k_gl4y with every
+// chunk in flight): 800 rows 9,648 futures/s (k_gl4y, 2 chains) vs 7,737 (k_gl4t, 3); 1,600 rows
+// 12,109 vs 12,172 (equal); 400 rows 6,165 vs 4,361.
+constexpr int64_t kSplitRows = 1200;
 int graph_linear_split_route(const GLArgs& a);  // v4 route of a layer: 0 one-kernel, 1 k_gl4y, 2 k_gl4t phases
 // Layers a and b (same x1 | x2, K and N, no RMS) on the tiled split route as one k_gl4t launch
 // over pr (N = 2 a.N: GLArgs::pair_n) and one mixing launch; bitwise equal to launching a and b
 // one after the other.  graph_linear_pair_ok: whether the pair launches (else launch a and b).
 bool graph_linear_pair_ok(const GLArgs& pr, const GLArgs& a, const GLArgs& b);
 hipError_t launch_graph_linear_pair_v4(const GLArgs& pr, const GLArgs& a, const GLArgs& b, hipStream_t s);
-int64_t split_rows_default();       // SKELDIFF_SPLIT_ROWS: auto split route at or below this many rows
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
 hipError_t launch_update(const UpdArgs& a, hipStream_t s);
 hipError_t launch_mix_mfma(const float* z, const float* G, float* out, int64_t rows, int J, int N, bool transpose,
@@ -180,7 +172,6 @@ hipError_t launch_convert_rows(void* dst, int dst_bf16, int64_t dst_rs, const vo
 hipError_t launch_philox_raw(uint32_t* out, int64_t rows, int64_t quads, uint64_t seed,
                              int64_t row0, int step, hipStream_t s);
 hipError_t launch_set_rng(uint64_t* rng_dev, uint64_t seed, int64_t row0, hipStream_t s);
-hipError_t launch_delay(double us, hipStream_t s);  // a stream-ordered wait of `us` microseconds
 hipError_t launch_copy_rows(float* dst, int64_t dst_rs, const float* src, int64_t src_rs,
                             int64_t rows, int64_t n, hipStream_t s);
 // row-blocked v4 activation layout -> row-major (rows, J, F)

@@ -14,7 +14,6 @@
 // All arithmetic is fp32; the GEMMs use the exact-f32 MFMA (a k-ordered fmaf chain).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "sd_internal.h"
 #include "sd_philox.h"
@@ -204,14 +203,6 @@ static hipError_t gl_dispatch_rms(const GLArgs& a, bool rms, hipStream_t s) {
         hipLaunchKernelGGL((k_graph_linear<JM, EXACT, NCB, false>), grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
-
-static int g_gl_variant = [] {
-    const char* e = getenv("SKELDIFF_GL_VARIANT");
-    const int x = e ? atoi(e) : 0;
-    return (x >= 0 && x <= 5) ? x : 0;
-}();
-
-int graph_linear_variant() { return g_gl_variant; }
 
 // 0 (default): v4 (f32-accurate split-f16 MFMA) where the plan prepared split weights and the
 // skeleton has an instantiation; otherwise the exact-f32 kernels per shape: v3 (node-split
@@ -597,26 +588,6 @@ __global__ void k_set_rng(uint64_t* rng, uint64_t seed, int64_t row0) {
     }
 }
 
-// One wave that waits `ticks` of the constant-rate wall clock (s_memrealtime), sleeping between
-// reads: a stream-ordered start offset for a row chain (sd_sample_loop's chain stagger).  Every
-// wave leaves once the clock has advanced, whatever the machine does.
-__global__ __launch_bounds__(64) void k_delay(uint64_t ticks) {
-    const uint64_t t0 = wall_clock64();
-    while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(16);
-}
-
-hipError_t launch_delay(double us, hipStream_t s) {
-    static const double ticks_per_us = [] {
-        int dev = 0, khz = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0)
-            khz = 100000;  // the MI355X constant clock: 100 MHz
-        return khz / 1000.0;
-    }();
-    if (us <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_delay, dim3(1), dim3(64), 0, s, (uint64_t)(us * ticks_per_us));
-    return hipGetLastError();
-}
-
 hipError_t launch_set_rng(uint64_t* rng_dev, uint64_t seed, int64_t row0, hipStream_t s) {
     hipLaunchKernelGGL(k_set_rng, dim3(1), dim3(64), 0, s, rng_dev, seed, row0);
     return hipGetLastError();
@@ -760,22 +731,6 @@ __global__ __launch_bounds__(256) void k_update(const UpdArgs p) {
         if (p.out2) st2(p.out2 + row * p.out2_rs + i * D + d, p.out_bf16 ? __builtin_convertvector(__builtin_convertvector(v, bf16x2), floatx2) : v);
         if (p.mean_out) st2(p.mean_out + row * p.mean_rs + i * D + d, mean);
     }
-    if (p.dump_x0) {  // diagnostics (sd_debug_update_dump)
-#pragma unroll
-        for (int j = 0; j < JM; ++j) {
-            if (!EXACT && j >= J) continue;
-            st2(p.dump_x0 + rb + j * D + d, x0v[j]);
-            st2(p.dump_xt + rb + j * D + d, xtv[j]);
-            st2(p.dump_ev + rb + j * D + d, ev[j]);
-        }
-    }
-#if defined(SD_DEBUG_LDS) && !defined(SD_DEBUG_NO_UPD)
-    {
-        unsigned bad = 0;
-        for (int i = (int)(g % DP); i < J * J; i += DP) bad += (sC1[i] != p.C1[i]) + (sC2[i] != p.C2[i]) + (sU[i] != p.U[i]);
-        if (bad) atomicAdd(&p.dbg[1], bad);
-    }
-#endif
 }
 
 // Small batches: k_update's thread owns a (row, feature pair) and walks all J nodes serially
@@ -868,16 +823,6 @@ __global__ __launch_bounds__(256) void k_update_row(const UpdArgs p) {
 // k_noise_fill) into LDS as sigma_j . eps; one barrier; then the MFMAs and the stores.
 // BF: x0 / x_t may be bf16 (precision mode 2); the f32 form has no bf16 load path at all (a
 // per-operand branch around the loads left the waitcnt pass's merged counts at vmcnt(0))
-#ifdef SD_UPD_STAMPS
-// diagnostic build only (tools/update_stamps.py): per workgroup of the full-batch k_update_mfma form,
-// thread 0's s_memrealtime at entry, after its loads are issued (tables stored), after phase A,
-// after the barrier, after the x0 prepass (its fragments arrived), after the MFMAs, after its stores
-// completed, and its CU id; overwritten by every launch (the last one of a call is read back)
-__device__ unsigned long long g_upd_stamps[4096 * 8];
-#define SD_UPD_STAMP(k, v) do { if (R == 4 && threadIdx.x == 0 && blockIdx.x < 4096) g_upd_stamps[blockIdx.x * 8 + (k)] = (v); } while (0)
-#else
-#define SD_UPD_STAMP(k, v) do { } while (0)
-#endif
 template <int JP, int R, int MT, bool BF = false>
 __global__ __launch_bounds__(256) void k_update_mfma(const UpdArgs p) {
     constexpr int KS = JP / 4, IB = JP / 16;
@@ -885,7 +830,6 @@ __global__ __launch_bounds__(256) void k_update_mfma(const UpdArgs p) {
     // {0, 1}) then hits 32 distinct banks; at a JP stride the 16 rows shared one or two banks (16-way
     // conflicts on every ds_read_b32 of the J <= 64 form, which re-reads its fragments per tile)
     constexpr int TSJ = JP + 2;
-    SD_UPD_STAMP(0, wall_clock64());
     const int J = p.J, D = p.D, JD = J * D, QPR = J * (D >> 2);  // quads per row
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* sTab = sm;                        // [3][JP][TSJ] zero-padded C1, C2, U
@@ -982,7 +926,6 @@ __global__ __launch_bounds__(256) void k_update_mfma(const UpdArgs p) {
         }
     }
     store_tables();
-    SD_UPD_STAMP(1, wall_clock64());
     // phase A: sigma_j eps_j (and the raw eps record) for the workgroup's rows (the first SGP
     // quads' sigma_j prefetched above: loaded in the loop, each was waited out right away).  One
     // loop per noise mode (a wave-uniform branch around whole loops): with the given-noise load and
@@ -1009,7 +952,6 @@ __global__ __launch_bounds__(256) void k_update_mfma(const UpdArgs p) {
         if (p.noise_out) *reinterpret_cast<floatx4*>(p.noise_out + rw * p.noise_rs + j * D + d) = e;
         if constexpr (NM != 0) e *= sg;
         *reinterpret_cast<floatx4*>(sEv + (rr * J + j) * DS + d) = e;
-        if (p.dump_ev) *reinterpret_cast<floatx4*>(p.dump_ev + rw * JD + j * D + d) = e;
     };
     auto run_a = [&](auto nm) {
 #pragma unroll
@@ -1021,9 +963,7 @@ __global__ __launch_bounds__(256) void k_update_mfma(const UpdArgs p) {
     if (p.noise_mode == 2) run_a(std::integral_constant<int, 2>{});
     else if (p.noise_mode == 1) run_a(std::integral_constant<int, 1>{});
     else run_a(std::integral_constant<int, 0>{});
-    SD_UPD_STAMP(2, wall_clock64());
     __syncthreads();
-    SD_UPD_STAMP(3, wall_clock64());
     if (!live) return;  // wave-uniform; no barrier follows
     // A fragments: lane (l16, l4) holds table[i = 16 ib + l16][j = 4 ks + l4]; JP <= 32: every
     // output block's fragments in registers for the whole row, JP = 64 (J <= 64): one block's at a
@@ -1051,30 +991,6 @@ __global__ __launch_bounds__(256) void k_update_mfma(const UpdArgs p) {
             if (p.act == 1) a = tanhf(a);
             bx[q][ks] = p.clip ? fminf(fmaxf(a, -1.f), 1.f) : a;
         }
-#ifdef SD_UPD_STAMPS
-    {  // the prepass's values in use: the x0 fragments have arrived
-        float chk = 0.f;
-#pragma unroll
-        for (int q = 0; q < MT; ++q)
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) chk += bx[q][ks];
-        SD_UPD_STAMP(4, wall_clock64() + (chk == 12345.f ? 1 : 0));
-    }
-#endif
-    if (p.dump_x0) {  // diagnostics (sd_debug_update_dump), apart from the tile loop (wave-uniform)
-#pragma unroll
-        for (int q = 0; q < MT; ++q) {
-            const int ct = ct0 + q * cstep;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const int j = 4 * ks + l4;
-                if (ct < nct && j < J) {
-                    p.dump_x0[rb + j * D + 16 * ct + l16] = bx[q][ks];
-                    p.dump_xt[rb + j * D + 16 * ct + l16] = bt[q][ks];
-                }
-            }
-        }
-    }
     // every tile's result first, then the stores back to back: with a tile's stores between its
     // MFMAs and the next tile's, the next tile reused the pending stores' data / address registers
     // and the waitcnt pass drained vmcnt(0) -- one store round trip -- per tile (15 such waits)
@@ -1115,16 +1031,6 @@ __global__ __launch_bounds__(256) void k_update_mfma(const UpdArgs p) {
                 *reinterpret_cast<floatx4*>(p.mean_out + row * p.mean_rs + i * D + 16 * ct + 4 * l4) = mean;
         }
     }
-#ifdef SD_UPD_STAMPS
-    {
-        float chk = 0.f;
-#pragma unroll
-        for (int q = 0; q < MT; ++q)
-#pragma unroll
-            for (int ib = 0; ib < IB; ++ib) chk += vres[q][ib][0];
-        SD_UPD_STAMP(5, wall_clock64() + (chk == 12345.f ? 1 : 0));
-    }
-#endif
 #pragma unroll
     for (int q = 0; q < MT; ++q) {
         const int ct = ct0 + q * cstep;
@@ -1146,19 +1052,10 @@ __global__ __launch_bounds__(256) void k_update_mfma(const UpdArgs p) {
             }
         }
     }
-#ifdef SD_UPD_STAMPS
-    __builtin_amdgcn_s_waitcnt(0);  // this wave's stores acknowledged
-    SD_UPD_STAMP(6, wall_clock64());
-    SD_UPD_STAMP(7, (unsigned long long)__smid());
-#endif
 }
 
-// rows at or below which launch_update runs k_update_row (process default SKELDIFF_UPDATE_ROWS)
-static int64_t g_update_rows = [] {
-    const char* e = getenv("SKELDIFF_UPDATE_ROWS");
-    return e ? (int64_t)atoll(e) : (int64_t)1024;
-}();
-
+// rows at or below which launch_update runs k_update_row
+constexpr int64_t kUpdateRows = 1024;
 
 hipError_t launch_update(const UpdArgs& a, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;
@@ -1166,7 +1063,7 @@ hipError_t launch_update(const UpdArgs& a, hipStream_t s) {
     // (SD_OPT_UPDATE_KERNEL; both give the same bits)
     const bool g_update_mfma = !a.elementwise;
     // the wave's column tiles (all of them in flight): D / 16 tiles over 4 / R waves, at most 6
-    const int Rm = a.B <= g_update_rows ? 1 : 4;
+    const int Rm = a.B <= kUpdateRows ? 1 : 4;
     if (g_update_mfma && !a.iso && a.J > 32 && a.J <= 64 && a.D % 16 == 0 && (a.D / 16 + 3) / 4 <= 2) {
         // J <= 64 (MANO J = 51 / 52): one row per workgroup, each wave at most two column tiles
         const size_t lds = (((3 * 64 * 66 + 3) & ~(size_t)3) + (size_t)a.J * (a.D + 16)) * sizeof(float);
@@ -1202,7 +1099,7 @@ hipError_t launch_update(const UpdArgs& a, hipStream_t s) {
         return R == 1 ? go(bf ? k_update_mfma<32, 1, 2, true> : k_update_mfma<32, 1, 2>, 32)
                       : go(bf ? k_update_mfma<32, 4, 6, true> : k_update_mfma<32, 4, 6>, 32);
     }
-    if (a.B <= g_update_rows && a.D % 2 == 0) {
+    if (a.B <= kUpdateRows && a.D % 2 == 0) {
         const size_t nt = a.iso ? 0 : 3 * (size_t)a.J * a.J + a.J;
         const size_t lds = (((nt + 3) & ~(size_t)3) + 3 * (size_t)a.J * a.D) * sizeof(float);
         if (lds <= 64 * 1024) {
@@ -1316,14 +1213,3 @@ hipError_t launch_sigma(const float* logvar, float* sig, int64_t n, hipStream_t 
 
 }  // namespace sd
 
-#ifdef SD_UPD_STAMPS
-extern "C" int sd_debug_update_stamps(unsigned long long* host, int nwg, int reset) {
-    if (reset) {
-        static unsigned long long zeros[4096 * 8] = {};
-        return hipMemcpyToSymbol(HIP_SYMBOL(sd::g_upd_stamps), zeros, sizeof(zeros)) == hipSuccess ? 0 : -3;
-    }
-    if (nwg < 0 || nwg > 4096) return -1;
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(sd::g_upd_stamps), (size_t)nwg * 8 * sizeof(unsigned long long)) ==
-                   hipSuccess ? 0 : -3;
-}
-#endif

@@ -1,11 +1,9 @@
 // Host side of libskeldiff: plan construction (state_dict-keyed tensor registry), one-time
 // packing, the per-step launch sequence of the Denoiser + posterior update, and the hipGraph
 // capture of the whole T-step chain.  Implements include/skeldiff.h.
-#include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdlib>
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -14,7 +12,6 @@
 #include <mutex>
 #include <numeric>
 #include <string>
-#include <tuple>
 #include <vector>
 
 #include "../../include/skeldiff.h"
@@ -32,24 +29,6 @@ int fail(int code, const std::string& msg) {
 }  // namespace
 
 int sd::set_error(int code, const std::string& msg) { return fail(code, msg); }
-int sd::diag_flags() {
-    static const int v = [] {
-        const char* e = getenv("SKELDIFF_DIAG");
-        return e ? atoi(e) : 0;
-    }();
-    return v;
-}
-
-#ifdef SD_DEBUG_LDS
-unsigned* sd::debug_counters() {
-    static unsigned* buf = [] {
-        unsigned* b = nullptr;
-        if (hipMalloc(&b, 8 * sizeof(unsigned)) != hipSuccess || hipMemset(b, 0, 8 * sizeof(unsigned)) != hipSuccess) abort();
-        return b;
-    }();
-    return buf;
-}
-#endif
 
 namespace {
 
@@ -114,40 +93,14 @@ struct GraphSet {
 
 }  // namespace
 
-// Diagnostics (tools/hazard_snap.py): when an arena is set (sd_debug_snapshot),
-// every graph-linear call of run_denoiser copies its phase-1 scratch Y (zs) and its output rows
-// into slot (step, call) of the arena at the chain's row offset, and the posterior update its
-// output into call slot kSnapCalls - 1, so a run with row chains can be compared slot by slot
-// with a one-chain run.  Never set on the product path.
-namespace {
-constexpr int kSnapCalls = 40;
-struct Snap {
-    float* arena = nullptr;
-    int64_t slot = 0, half = 0;  // floats per slot; the Y region is [0, half), the output region the rest
-    int nslots = 0;
-    std::vector<int> meta;  // per slot: N, output floats per row, Y floats per row
-};
-Snap g_snap;
-// diagnostics (sd_debug_update_dump): the first update of a sampling call dumps its inputs
-struct UpdDump {
-    float *x0 = nullptr, *xt = nullptr, *ev = nullptr;
-};
-UpdDump g_dump;
-}  // namespace
-
 // Row chains.  Rows never interact inside the Denoiser or the posterior update, so the T-step
 // chain of rows [r0, r1) is independent of every other row range: record_loop splits the batch
 // into `chains` row ranges (multiples of 32 rows) and records each range's
 // T steps on its own stream, forked from and joined back into the caller's stream.  Kernels of
 // different chains then run concurrently, so one chain's idle CUs (a 200-workgroup graph linear
 // on 256 CUs, the last wave of a 800-workgroup attention launch) take the other chain's
-// workgroups instead of waiting for the next kernel boundary.
-static const int g_chains = [] {
-    const char* e = getenv("SKELDIFF_CHAINS");
-    const int v = e ? atoi(e) : 0;
-    return (v >= 0 && v <= 8) ? v : 0;  // 0: per batch size (chain_count)
-}();
-
+// workgroups instead of waiting for the next kernel boundary.  SD_OPT_ROW_CHAINS sets the
+// count; 0 (a new plan's value) chooses it per batch size (chain_count).
 
 struct sd_plan {
     sd_plan_desc d{};
@@ -159,7 +112,7 @@ struct sd_plan {
     bool fuse_ok = false;  // to_qkv + attention fusable (v4 split weights, J <= 17 or 21, dim_head 32)
     bool blk_ok = false;   // every layer on v4 with row-blocked intermediate activations
     int prec = 0;          // sd_plan_set_precision: 0 f32-accurate, 1 half (f16 products)
-    // kernel options (sd_plan_set_option), initialised from the process defaults at creation
+    // kernel options (sd_plan_set_option); 0 = auto, the only way a plan's kernels are chosen
     int variant = 0, gl4_cfg = 0, gl4_stage = 0, split = 0, chains = 0;
     int upd_elem = 0;  // SD_OPT_UPDATE_KERNEL: 1 = the element-per-thread update forms
     int v5_valu = 0;   // SD_OPT_V5_MIX: 1 = the VALU mixing pass of v5
@@ -367,9 +320,6 @@ sd::GLArgs gl_args(const sd_plan* p, const GL& g, const float* x1, int x1_div, c
     a.gl4_stage = p->gl4_stage;
     a.split = p->split;
     a.v5_valu = p->v5_valu;
-#ifdef SD_DEBUG_LDS
-    a.dbg = sd::debug_counters();
-#endif
     return a;
 }
 
@@ -404,27 +354,8 @@ struct Prof {
 int run_denoiser(const sd_plan* p, const float* x_t, const float* x_cond, int64_t cond_repeat,
                  int t, float* x0_out, int64_t rows, const WS& w, hipStream_t s, Prof* prof = nullptr,
                  int64_t cond_phase = 0, int tile_hint = 0, float* const* trace = nullptr,
-                 int xt_bf16 = 0, int x0_bf16 = 0, int64_t route_rows = 0, int64_t snap_r0 = -1,
-                 int snap_step = 0) {
+                 int xt_bf16 = 0, int x0_bf16 = 0, int64_t route_rows = 0) {
     const int H = p->H;
-    int snap_call = 0;
-    auto snap = [&](const sd::GLArgs& g) -> int {
-        const int call = snap_call++;
-        if (!g_snap.arena || snap_r0 < 0) return SD_OK;
-        const int64_t sl = (int64_t)snap_step * kSnapCalls + call;
-        if (sl >= g_snap.nslots) return SD_OK;
-        float* base = g_snap.arena + sl * g_snap.slot;
-        const int64_t yrow = (int64_t)p->J * g.N;
-        g_snap.meta[3 * sl] = g.N;
-        g_snap.meta[3 * sl + 1] = (int)g.out_rs;
-        g_snap.meta[3 * sl + 2] = (int)yrow;
-        if (g.zs && (snap_r0 + rows) * yrow <= g_snap.half)
-            SD_HIP(hipMemcpyAsync(base + snap_r0 * yrow, g.zs, rows * yrow * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if ((snap_r0 + rows) * g.out_rs <= g_snap.slot - g_snap.half)
-            SD_HIP(hipMemcpyAsync(base + g_snap.half + snap_r0 * g.out_rs, g.out, rows * g.out_rs * sizeof(float),
-                                  hipMemcpyDeviceToDevice, s));
-        return SD_OK;
-    };
     // v4 path: every intermediate activation in the row-blocked layout (coalesced x fragments);
     // the denoiser's inputs (x_t, x_cond) and output (x0) stay row-major
     const int B = p->blocked_now() ? 1 : 0;
@@ -477,9 +408,7 @@ int run_denoiser(const sd_plan* p, const float* x_t, const float* x_cond, int64_
     }
     lay(a, 0, 0, 1);
     SD_LAUNCH(prof, 0, sd::launch_graph_linear(a, false, s));
-    int rc = snap(a);
-    if (rc) return rc;
-    rc = record(w.r);
+    int rc = record(w.r);
     if (rc) return rc;
 
     const int L = 2 * p->depth;
@@ -491,12 +420,10 @@ int run_denoiser(const sd_plan* p, const float* x_t, const float* x_cond, int64_
         lay(a, 1, 1, 1);
         a.act = 1;
         SD_LAUNCH(prof, 0, sd::launch_graph_linear(a, false, s));
-        if ((rc = snap(a))) return rc;
         a = gl_args(p, p->r2[l], w.h, 1, nullptr, nullptr, xin, w.x, rows);
         lay(a, 1, 1, 1);
         a.act = 1;
         SD_LAUNCH(prof, 0, sd::launch_graph_linear(a, false, s));
-        if ((rc = snap(a))) return rc;
         if ((rc = record(w.x))) return rc;
         if (!p->has_attn[l]) {
             if ((rc = record(w.x))) return rc;  // nn.Identity in place of the last attention
@@ -517,7 +444,6 @@ int run_denoiser(const sd_plan* p, const float* x_t, const float* x_cond, int64_
                 fused = sd::launch_qkv_attention_v4(a, true, s);
                 if (fused != hipSuccess && fused != hipErrorNotSupported) SD_HIP(fused);
                 if (prof && prof->post(s)) return fail(SD_E_HIP, "hipEventRecord failed");
-                if (fused == hipSuccess && (rc = snap(a))) return rc;
             }
             if (fused == hipErrorNotSupported) {
                 if (B) return fail(SD_E_INTERNAL, "row-blocked plan without the fused attention kernel");
@@ -534,7 +460,6 @@ int run_denoiser(const sd_plan* p, const float* x_t, const float* x_cond, int64_
                 }
                 SD_HIP(ge);
                 if (prof && prof->post(s)) return fail(SD_E_HIP, "hipEventRecord failed");
-                if ((rc = snap(a))) return rc;
                 sd::AttnArgs aa{w.qkv, w.o, rows, p->J, p->d.attn_heads, p->d.attn_dim_head, qscale,
                                 a.skip_mix ? a.G : nullptr};
                 SD_LAUNCH(prof, 1, sd::launch_attention(aa, s));
@@ -542,7 +467,6 @@ int run_denoiser(const sd_plan* p, const float* x_t, const float* x_cond, int64_
             a = gl_args(p, p->outp[l], w.o, 1, nullptr, nullptr, w.x, w.x, rows);
             lay(a, 1, 1, 1);
             SD_LAUNCH(prof, 0, sd::launch_graph_linear(a, false, s));
-            if ((rc = snap(a))) return rc;
         } else {
             // Residual(PreNorm(StaticGraphLinear)): x = GL(rmsnorm(x)) + x, written to the `o`
             // buffer (sized like x in this configuration: a graph-linear may not write its own
@@ -550,7 +474,6 @@ int run_denoiser(const sd_plan* p, const float* x_t, const float* x_cond, int64_
             a = gl_args(p, p->qkv[l], w.x, 1, nullptr, nullptr, w.x, w.o, rows);
             lay(a, 1, 1, 1);
             SD_LAUNCH(prof, 0, sd::launch_graph_linear(a, true, s));
-            if ((rc = snap(a))) return rc;
             const int64_t rp = B ? (rows + 31) / 32 * 32 : rows;
             SD_LAUNCH(prof, 0, sd::launch_convert_rows(w.x, bfl(w.x), (int64_t)p->J * H, w.o, bfl(w.o), (int64_t)p->J * H, rp,
                                                        (int64_t)p->J * H, s));
@@ -583,20 +506,16 @@ int run_denoiser(const sd_plan* p, const float* x_t, const float* x_cond, int64_
         }
     }
     if (!paired) SD_LAUNCH(prof, 0, sd::launch_graph_linear(a, false, s));
-    if ((rc = snap(a))) return rc;
     if (!paired) SD_LAUNCH(prof, 0, sd::launch_graph_linear(b1, false, s));
-    if ((rc = snap(b1))) return rc;
     a = gl_args(p, p->r2[L], w.h, 1, nullptr, nullptr, w.res, w.res, rows);
     lay(a, 1, 1, 1);
     a.act = 1;
     SD_LAUNCH(prof, 0, sd::launch_graph_linear(a, false, s));
-    if ((rc = snap(a))) return rc;
     if ((rc = record(w.res))) return rc;
     // final_glin (generator.py:107)
     a = gl_args(p, p->fglin, w.res, 1, nullptr, nullptr, nullptr, x0_out, rows);
     lay(a, 1, 1, 0);
     SD_LAUNCH(prof, 0, sd::launch_graph_linear(a, false, s));
-    if ((rc = snap(a))) return rc;
     return SD_OK;
 }
 
@@ -634,12 +553,6 @@ int run_update(const sd_plan* p, const float* x0, const float* xt, const float* 
     u.J = p->J;
     u.D = p->D;
     u.elementwise = p->upd_elem == 1;
-#ifdef SD_DEBUG_LDS
-    u.dbg = sd::debug_counters();
-#endif
-    u.dump_x0 = g_dump.x0;
-    u.dump_xt = g_dump.xt;
-    u.dump_ev = g_dump.ev;
     if (p->d.isotropic) {
         u.c1s = p->iso_c1[t];
         u.c2s = p->iso_c2[t];
@@ -691,30 +604,6 @@ int32_t sd_abi_version(void) { return SD_ABI_VERSION; }
 #endif
 const char* sd_build_info(void) { return SD_BUILD_INFO; }
 
-// Diagnostics only (tools/hazard_snap.py; not in include/skeldiff.h): set (arena != null) or clear
-// the snapshot arena of run_denoiser / record_loop.  slot_floats per slot, the first y_floats of
-// it for the phase-1 scratch Y.  Not thread-safe; never used by the product path.
-int sd_debug_snapshot(float* arena, int64_t slot_floats, int64_t y_floats, int32_t nslots) {
-    g_snap.arena = arena;
-    g_snap.slot = slot_floats;
-    g_snap.half = y_floats;
-    g_snap.nslots = arena ? nslots : 0;
-    g_snap.meta.assign(3 * (size_t)std::max(nslots, 0), 0);
-    return SD_OK;
-}
-// Diagnostics only: the first posterior update of the next sampling calls stores its inputs
-// (x0 after activation and clamp, x_t, sigma eps; (rows, J, D) each) to these buffers; nulls = off
-int sd_debug_update_dump(float* x0, float* xt, float* ev) {
-    g_dump = UpdDump{x0, xt, ev};
-    if (!x0 || !xt || !ev) g_dump = UpdDump{};
-    return SD_OK;
-}
-int sd_debug_snapshot_meta(int32_t slot, int32_t* out3) {
-    if (slot < 0 || 3 * (size_t)slot + 2 >= g_snap.meta.size()) return SD_E_INVALID;
-    for (int i = 0; i < 3; ++i) out3[i] = g_snap.meta[3 * (size_t)slot + i];
-    return SD_OK;
-}
-
 const char* sd_last_error(void) { return g_err.c_str(); }
 
 int sd_plan_create(sd_plan** out, const sd_plan_desc* desc) {
@@ -723,15 +612,6 @@ int sd_plan_create(sd_plan** out, const sd_plan_desc* desc) {
     int rc = check_dims(desc);
     if (rc) return rc;
     std::unique_ptr<sd_plan> p(new sd_plan());
-    p->variant = sd::graph_linear_variant();
-    if (desc->norm_type == 1 && p->variant != 0 && p->variant != 4)
-        return fail(SD_E_INVALID, "norm_type 'layer' runs on the v4 kernels only (SKELDIFF_GL_VARIANT 0 or 4)");
-    p->gl4_cfg = sd::gl4_tile_default();
-    p->gl4_stage = sd::gl4_stage_default();
-    p->chains = g_chains;
-#ifdef SD_DEBUG_LDS
-    (void)sd::debug_counters();  // allocated here, never during a stream capture
-#endif
     p->d = *desc;
     p->J = desc->num_nodes;
     p->D = desc->latent_dim;
@@ -1103,9 +983,9 @@ static int chain_count(const sd_plan* p, int64_t rows, int64_t cond_repeat, int6
     // kernel is a few microseconds long and a second chain slows both (config 4, 50 rows: 61 vs
     // 106 futures/s; tools/sweep_routes.py, profiles/r03/ab)
     int n = p->chains > 0 ? std::min(p->chains, (int)sd_plan::kMaxChains)
-            : rows <= 128                       ? 1
-            : rows <= sd::split_rows_default() ? 2
-                                               : 3;
+            : rows <= 128            ? 1
+            : rows <= sd::kSplitRows ? 2
+                                     : 3;
     if (units < n) n = (int)std::max<int64_t>(1, units);
     return n;
 }
@@ -1121,10 +1001,7 @@ static int64_t chain_row(int i, int n, int64_t rows, int64_t unit) {
 // keeps two full 256-row workgroups; below that the 32-row cuts stay (so do the small batches'
 // chain shapes).  Rows are independent and the Philox rows / x_cond phase follow r0, so the
 // results do not depend on where the cuts fall.
-#ifndef SD_CHAIN_TILE_UNIT
-#define SD_CHAIN_TILE_UNIT 128
-#endif
-constexpr int64_t kChainTileUnit = SD_CHAIN_TILE_UNIT;
+constexpr int64_t kChainTileUnit = 128;
 static_assert(kChainTileUnit >= 32 && kChainTileUnit % 32 == 0, "chains start on 32-row blocks");
 static int64_t chain_start(int64_t rows, int n, int64_t unit, int i) {
     if (n < 1) n = 1;
@@ -1154,29 +1031,10 @@ int64_t sd_chain_start(int64_t rows, int32_t nchains, int64_t unit, int32_t i) {
 int64_t sd_chain_tile_unit(void) { return kChainTileUnit; }
 
 // Creates the auxiliary streams / fork-join events chains 1 .. n-1 use (caller holds cmu).
-// Diagnostics (SKELDIFF_DIAG bit 13): every chain, the first included, on a stream
-// of its own whose CU mask is a disjoint 1/n of the device's CUs (no two chains share a CU).
-constexpr int kDiagCuMask = 1 << 13;
 static int ensure_chains(sd_plan* mp, int n) {
-    const bool masked = sd::diag_flags() & kDiagCuMask;
     if (!mp->ev_fork) SD_HIP(hipEventCreateWithFlags(&mp->ev_fork, hipEventDisableTiming));
-    for (int i = masked ? 0 : 1; i < n; ++i) {
-        if (!mp->aux[i]) {
-            if (masked) {
-                int dev = 0;
-                hipDeviceProp_t pr;
-                SD_HIP(hipGetDevice(&dev));
-                SD_HIP(hipGetDeviceProperties(&pr, dev));
-                const int ncu = pr.multiProcessorCount;
-                std::vector<uint32_t> m((ncu + 31) / 32, 0u);
-                const bool inter = sd::diag_flags() & (1 << 17);  // bit 17: interleaved (cu % n == i)
-                for (int c = 0; c < ncu; ++c)
-                    if (inter ? c % n == i : c * n / ncu == i) m[c / 32] |= 1u << (c % 32);
-                SD_HIP(hipExtStreamCreateWithCUMask(&mp->aux[i], (uint32_t)m.size(), m.data()));
-            } else {
-                SD_HIP(hipStreamCreateWithFlags(&mp->aux[i], hipStreamNonBlocking));
-            }
-        }
+    for (int i = 1; i < n; ++i) {
+        if (!mp->aux[i]) SD_HIP(hipStreamCreateWithFlags(&mp->aux[i], hipStreamNonBlocking));
         if (!mp->ev_join[i]) SD_HIP(hipEventCreateWithFlags(&mp->ev_join[i], hipEventDisableTiming));
     }
     return SD_OK;
@@ -1225,24 +1083,16 @@ static int record_loop(const sd_plan* p, const float* x_T, const float* x_cond, 
             // 5 % faster than the single-chain 32 x 96 choice at B = 3200, 3 chains
             const int64_t wg813 = (c.n + 31) / 32 * 2;  // 32 x 96 workgroups of an N = 192 layer
             int rc = run_denoiser(p, c.cur, xc, cond_repeat, t, c.w.x0, c.n, c.w, cs[i], nullptr, r0 % cond_repeat,
-                                  (nch > 1 && wg813 >= 32) ? 812 : 0, nullptr, bf, bf, rows, r0, (int)k);
+                                  (nch > 1 && wg813 >= 32) ? 812 : 0, nullptr, bf, bf, rows);
             if (rc) return rc;
             float* nxt = (t == 0) ? out + r0 * JD : (((T - 1 - t) & 1) ? c.w.img1 : c.w.img0);
             const float* eps = (!dev_noise && t > 0) ? eps_all + r0 * step_rs + k * JD : nullptr;
-            const UpdDump saved = g_dump;
-            if (k != 0 || !g_dump.x0) g_dump = UpdDump{};
-            else g_dump = UpdDump{g_dump.x0 + r0 * JD, g_dump.xt + r0 * JD, g_dump.ev + r0 * JD};
             rc = run_update(p, c.w.x0, c.cur, eps, step_rs, dev_noise ? 2 : 1, seed, row0, rng, t, nxt,
                             (rec && timages) ? timages + r0 * step_rs + k * JD : nullptr, step_rs,
                             (rec && means) ? means + r0 * step_rs + k * JD : nullptr, step_rs,
                             (rec && noise_out) ? noise_out + r0 * step_rs + k * JD : nullptr, step_rs, c.n,
                             cs[i], nullptr, r0, bf, bf, t > 0 ? bf : 0, !(flags & SD_FLAG_NO_CLIP));
-            g_dump = saved;
             if (rc) return rc;
-            const int64_t sl = k * kSnapCalls + kSnapCalls - 1;  // diagnostics: the update's output
-            if (g_snap.arena && sl < g_snap.nslots && (r0 + c.n) * JD <= g_snap.slot - g_snap.half)
-                SD_HIP(hipMemcpyAsync(g_snap.arena + sl * g_snap.slot + g_snap.half + r0 * JD, nxt, c.n * JD * sizeof(float),
-                                      hipMemcpyDeviceToDevice, cs[i]));
             c.cur = nxt;
         }
     }
@@ -1252,19 +1102,15 @@ static int record_loop(const sd_plan* p, const float* x_T, const float* x_cond, 
 // fork chains 1 .. n-1 off s (caller holds cmu, ensure_chains done)
 static int fork_chains(sd_plan* mp, hipStream_t s, int n, hipStream_t* cs) {
     cs[0] = s;
-    if (sd::diag_flags() & 4) {  // diagnostic: every chain on the caller's stream (no concurrency)
-        for (int i = 1; i < n; ++i) cs[i] = s;
-        return SD_OK;
-    }
     if (n > 1) SD_HIP(hipEventRecord(mp->ev_fork, s));
-    for (int i = (n > 1 && (sd::diag_flags() & kDiagCuMask)) ? 0 : 1; i < n; ++i) {
+    for (int i = 1; i < n; ++i) {
         SD_HIP(hipStreamWaitEvent(mp->aux[i], mp->ev_fork, 0));
         cs[i] = mp->aux[i];
     }
     return SD_OK;
 }
 static int join_chains(sd_plan* mp, hipStream_t s, int n, const hipStream_t* cs) {
-    for (int i = (n > 1 && (sd::diag_flags() & kDiagCuMask)) ? 0 : 1; i < n; ++i) {
+    for (int i = 1; i < n; ++i) {
         SD_HIP(hipEventRecord(mp->ev_join[i], cs[i]));
         SD_HIP(hipStreamWaitEvent(s, mp->ev_join[i], 0));
     }
@@ -1301,7 +1147,6 @@ int sd_sample_loop(const sd_plan* p, const float* x_T, const float* x_cond, int6
         lk.lock();
         if ((rc = ensure_chains(mp, nch))) return rc;
         for (int i = 1; i < nch; ++i) cs[i] = mp->aux[i];
-        if (sd::diag_flags() & kDiagCuMask) cs[0] = mp->aux[0];
     }
     if (!(flags & SD_FLAG_GRAPH)) {
         if ((rc = fork_chains(mp, s, nch, cs))) return rc;
@@ -1381,16 +1226,9 @@ int sd_sample_loop(const sd_plan* p, const float* x_T, const float* x_cond, int6
     mp->last_route.store(set->route_bits);
     if ((rc = fork_chains(mp, s, nch, cs))) return rc;
     {
-        // SKELDIFF_CHAIN_STAGGER (µs, A/B): chain i starts i x that much later, so the chains run
-        // different layer types at a time instead of the same one in lockstep
-        static const double stagger = [] {
-            const char* e = getenv("SKELDIFF_CHAIN_STAGGER");
-            return e ? atof(e) : 0.0;
-        }();
         std::lock_guard<std::mutex> g(set->mu);
         for (int i = 0; i < nch; ++i) {
             SD_HIP(hipStreamWaitEvent(cs[i], set->done[i], 0));  // the exec's previous launch (any stream)
-            if (i > 0 && stagger > 0) SD_HIP(sd::launch_delay(stagger * i, cs[i]));
             SD_HIP(hipGraphLaunch(set->execs[i], cs[i]));
             SD_HIP(hipEventRecord(set->done[i], cs[i]));
         }
@@ -1534,9 +1372,7 @@ int sd_best_sample(const float* pred, const float* target, int64_t nseq, int32_t
 }
 
 // kernel generation / v4 tile of the sd_test_* hooks only (plans take theirs from SD_OPT_*)
-static int g_test_variant = -1, g_test_tile = -1;  // -1: the process defaults (SKELDIFF_* at load)
-static int test_variant() { return g_test_variant >= 0 ? g_test_variant : sd::graph_linear_variant(); }
-static int test_tile() { return g_test_tile >= 0 ? g_test_tile : sd::gl4_tile_default(); }
+static int g_test_variant = 0, g_test_tile = 0;  // 0: auto
 
 // split route of the test entry points (GLArgs::split: 0 auto, 1 never, 2 k_gl4y, 3 k_gl4t, 4 k_gl4t
 // except to_qkv + attention); 2 / 3 / 4 give sd_test_graph_linear* a scratch of its own for the pre-mix Y
@@ -1550,9 +1386,9 @@ int sd_test_set_split_route(int32_t route) {
 }
 
 int sd_test_set_kernel_variant(int32_t gl_variant, int32_t gl4_tile) {
-    if (gl_variant == -1) return test_variant();  // query
+    if (gl_variant == -1) return g_test_variant;  // query
     if (gl_variant < 0 || gl_variant > 5) return fail(SD_E_INVALID, "gl_variant out of range");
-    const int old = test_variant();
+    const int old = g_test_variant;
     g_test_variant = gl_variant;
     if (gl4_tile >= 0) g_test_tile = gl4_tile;
     return old;
@@ -1691,30 +1527,15 @@ int sd_test_graph_linear_layout(const float* x1, int32_t K1, int64_t x1_div, con
         a.ntype[j] = (int)node_types[j];
         a.ntypes = std::max(a.ntypes, (int)node_types[j] + 1);
     }
-    // split weights for v4: made per call (tests), or cached by W pointer when
-    // SKELDIFF_GL_CACHE_SPLIT=1 (tools/bench_gl.py: weights fixed across timed calls)
-    static const bool cache = [] {
-        const char* e = getenv("SKELDIFF_GL_CACHE_SPLIT");
-        return e && atoi(e) == 1;
-    }();
-    static std::map<std::tuple<const float*, int, int, int>, sd::SplitW> cached;
     a.x1_blk = layout & 1;
     a.x2_blk = (layout >> 1) & 1;
     a.res_blk = (layout >> 2) & 1;
     a.out_blk = (layout >> 3) & 1;
-    a.variant = test_variant();
-    a.gl4_cfg = test_tile();
-    a.gl4_stage = sd::gl4_stage_default();
-    sd::SplitW sw;
+    a.variant = g_test_variant;
+    a.gl4_cfg = g_test_tile;
+    sd::SplitW sw;  // split weights for v4, made and freed per call
     if (a.variant == 0 || a.variant == 4) {
-        const auto key = std::make_tuple(W, a.ntypes, N, K1 + a.K2);
-        auto it = cache ? cached.find(key) : cached.end();
-        if (it != cached.end()) {
-            sw = it->second;
-        } else {
-            SD_HIP(sd::make_split_weights(W, a.ntypes, N, K1 + a.K2, &sw, (hipStream_t)stream));
-            if (cache) cached[key] = sw;
-        }
+        SD_HIP(sd::make_split_weights(W, a.ntypes, N, K1 + a.K2, &sw, (hipStream_t)stream));
         a.wsp = sw.w;
         a.wsp_nct = sw.nct;
         a.wsp_unscale = sw.unscale;
@@ -1727,9 +1548,9 @@ int sd_test_graph_linear_layout(const float* x1, int32_t K1, int64_t x1_div, con
         a.zs = zs;
     }
     const hipError_t e = sd::launch_graph_linear(a, rms != 0, (hipStream_t)stream);
-    if ((sw.w && !cache) || zs) {
+    if (sw.w || zs) {
         (void)hipStreamSynchronize((hipStream_t)stream);
-        if (sw.w && !cache) (void)hipFree(sw.w);
+        if (sw.w) (void)hipFree(sw.w);
         if (zs) (void)hipFree(zs);
     }
     SD_HIP(e);
@@ -1762,9 +1583,8 @@ int sd_test_qkv_attention(const float* x, int32_t K, const float* W, const int64
     }
     a.attn_heads = heads;
     a.attn_scale = (float)std::pow(32.0, -0.5);
-    a.variant = test_variant();
-    a.gl4_cfg = test_tile();
-    a.gl4_stage = sd::gl4_stage_default();
+    a.variant = g_test_variant;
+    a.gl4_cfg = g_test_tile;
     a.x1_blk = layout & 1;
     a.out_blk = (layout >> 3) & 1;
     sd::SplitW sw;
@@ -1788,16 +1608,6 @@ int sd_test_attention(const float* qkv, float* out, int64_t rows, int32_t J, int
     SD_HIP(sd::launch_attention(aa, (hipStream_t)stream));
     return SD_OK;
 }
-
-#ifdef SD_DEBUG_LDS
-// diagnostic build only: copy the LDS integrity counters to out[8] (host), then zero them
-int sd_debug_lds_counters(uint32_t* out) {
-    SD_HIP(hipDeviceSynchronize());
-    SD_HIP(hipMemcpy(out, sd::debug_counters(), 8 * sizeof(unsigned), hipMemcpyDeviceToHost));
-    SD_HIP(hipMemset(sd::debug_counters(), 0, 8 * sizeof(unsigned)));
-    return SD_OK;
-}
-#endif
 
 int sd_noise_fill(float* out, int64_t rows, int64_t n_per_row, uint64_t seed, int64_t row0, int32_t step,
                   void* stream) {

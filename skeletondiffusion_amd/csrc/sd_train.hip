@@ -261,12 +261,6 @@ __global__ __launch_bounds__(256) void k_gemm(GemmArgs g) {
 // One workgroup per (row, 64-column chunk): the J x 64 input slab and M^T in LDS; each thread owns
 // one column and RPT consecutive output rows (RPT * 4 >= J), fed per source node by one LDS read
 // of the input and RPT / 4 16-B broadcast reads of M^T[j][i0 ..] (not two LDS reads per FMA).
-// SKELDIFF_TRAIN_MIX=0 at load: the per-column k_mix everywhere (A/B)
-static int g_train_mix_mfma = [] {
-    const char* e = getenv("SKELDIFF_TRAIN_MIX");
-    return e ? atoi(e) : 1;
-}();
-
 template <int RPT>
 __global__ __launch_bounds__(256) void k_mix(const float* __restrict__ in, const float* __restrict__ ghat,
                                              float* __restrict__ out, int J, int N, int transpose) {
@@ -310,7 +304,7 @@ hipError_t launch_mix(const float* in, const float* ghat, float* out, int64_t ro
     // the matrix-core mixing pass (sd_graph_linear_v5.hip, k_gl5_mixm) for J > 32, where at least
     // three of its four waves own output nodes (at J = 16 three of four idle: 27.9 vs 15.8 us per
     // launch for the per-column form below, profiles/train_r03); the same fmaf chains
-    if (g_train_mix_mfma && J > 32) {
+    if (J > 32) {
         const hipError_t e = launch_mix_mfma(in, ghat, out, rows, J, N, transpose != 0, s);
         if (e != hipErrorNotSupported) return e;
     }

@@ -3,6 +3,7 @@ and its host-side argument validation behaves (no device call happens on these p
 import ctypes
 import os
 import re
+import subprocess
 
 from conftest import REPO
 from skeletondiffusion_amd import _lib
@@ -27,6 +28,38 @@ def test_library_exports_every_declared_symbol():
     assert lib.sd_abi_version() == _lib.SD_ABI_VERSION == 4
     hdr = open(os.path.join(os.path.dirname(__file__), "..", "include", "skeldiff.h")).read()
     assert re.search(r"#define SD_ABI_VERSION (\d+)", hdr).group(1) == str(_lib.SD_ABI_VERSION)
+
+
+def defined_dynamic_symbols(path):
+    """Names of the defined dynamic symbols of a shared library: `llvm-nm -D --defined-only`, or
+    where the ROCm LLVM tools come without llvm-nm, the same table from `llvm-readelf --dyn-syms`."""
+    from skeletondiffusion_amd import isa_check
+
+    def run(tool, *args):
+        return subprocess.run([isa_check._tool(tool), *args, path], check=True, capture_output=True, text=True).stdout
+
+    try:
+        return {line.split()[-1] for line in run("llvm-nm", "-D", "--defined-only").splitlines() if line.split()}
+    except RuntimeError:  # isa_check._tool: no such tool
+        rows = (line.split() for line in run("llvm-readelf", "--dyn-syms", "-W").splitlines())
+        return {r[7].split("@")[0] for r in rows if len(r) == 8 and r[0].endswith(":") and r[6] != "UND"}
+
+
+def test_library_exports_only_declared_symbols():
+    """The library's defined dynamic sd_* symbols are exactly the header's: no undeclared
+    diagnostic entry point rides along in the product."""
+    exported = sorted(n for n in defined_dynamic_symbols(_lib.LIB_PATH) if n.startswith("sd_"))
+    assert exported == declared_symbols()
+
+
+def test_no_getenv_in_csrc():
+    """Kernels, thresholds and routes are chosen by a plan's options alone: the library's sources
+    read no environment variable."""
+    csrc = os.path.join(REPO, "skeletondiffusion_amd", "csrc")
+    files = [os.path.join(d, f) for d, _, fs in os.walk(csrc) for f in fs]
+    assert files
+    hits = [f for f in sorted(files) if "getenv(" in open(f, errors="replace").read()]
+    assert hits == []
 
 
 def test_invalid_desc_is_rejected_on_host():

@@ -1,7 +1,7 @@
-"""Summarise tools/pmc_gl.sh / tools/pmc_kernel.sh output: MFMA utilisation, stall split,
+"""Summarise tools/pmc_kernel.sh output: MFMA utilisation, stall split,
 instruction mix, LDS bank conflicts.
-usage: python tools/pmc_report.py [--kernel REGEX] [--dir PATTERN] tag [tag ...]
-(defaults: the graph-linear kernels, gpurun_out/pmc_gl_<tag>)"""
+usage: python tools/pmc_report.py [--kernel REGEX] --dir PATTERN tag [tag ...]
+(PATTERN: the output directory of a tag's passes, {tag} replaced; default kernels: the graph-linear ones)"""
 import argparse
 import collections
 import csv
@@ -10,7 +10,7 @@ import re
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--kernel", default=r"k_gl|k_graph_linear")
-ap.add_argument("--dir", default="gpurun_out/pmc_gl_{tag}")
+ap.add_argument("--dir", required=True, help="output directory of a tag's passes; {tag} is replaced")
 ap.add_argument("--raw", action="store_true", help="also print every counter's per-dispatch average")
 ap.add_argument("tags", nargs="+")
 args = ap.parse_args()
