@@ -29,6 +29,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "sd_gl4_args.h"
 #include "sd_internal.h"
 
 namespace sd {
@@ -202,10 +203,19 @@ hipError_t make_split_weights(const float* W, int ntypes, int N, int K, SplitW* 
 // whole by one wave and read back in 1-2 KiB runs by the mixing phase -- round 4; it was
 // [tile][node][32 rows][N], 128-B runs); (ROWMAJOR, v5 for J > 21) row-major z with y_cs = 32,
 // rows < B only.
-struct YOut {
+struct YDst {  // host side: where a GEMM phase writes (packed into GL4GArgs by the launchers)
     float* y;
     int64_t y_rs, y_js, y_ts, y_cs;
 };
+// k_gl4t's argument block.  The kernel's parameter list keeps the types it always had -- (GLArgs, int,
+// long, YOut): tests/test_isa_waits.py finds the kernel by that symbol -- but reads this block alone;
+// the three leading parameters are dead (never loaded: kernel arguments stay in memory until read).
+// (Behind GLArgs, int and long the block starts 16 bytes into a line of the argument segment;
+// alignas(64) on it measured no faster)
+struct YOut {
+    GL4GArgs g;
+};
+static_assert(sizeof(YOut) == sizeof(GL4GArgs), "YOut: the GEMM-phase block");
 // zs element (row, node j, column n) of the split route's column-tiled scratch
 __device__ __forceinline__ int64_t zs_off(int64_t row, int j, int n, int J, int N) {
     return ((((row >> 5) * (N >> 5) + (n >> 5)) * J + j) << 10) + ((row & 31) << 5) + (n & 31);
@@ -263,17 +273,30 @@ __device__ __forceinline__ floatx16 exact_tile_f32(const GLArgs& p, int64_t row0
                                p.J, p.W, p.wrow[j], p.N, p.wsp_unscale, row0, j, col0);
 }
 
+// Everything of the block that feeds the first operand addresses, asked for in one batch of scalar
+// loads at kernel entry (its first three lines; one wait): left to the compiler, the loads sat next
+// to their uses, 6 - 7 dependent kernel-argument round trips before the first fill.
+__device__ __forceinline__ void gl4g_preload(const GL4GArgs& p) {
+    asm volatile("" ::"s"(p.da.d), "s"(p.da.m), "s"(p.db.d), "s"(p.db.m), "s"(p.q8), "s"(p.r8), "s"(p.J), "s"(p.N), "s"(p.wsp),
+                 "s"(p.x1), "s"(p.x2), "s"(p.bias), "s"(p.B), "s"(p.ntile_r), "s"(p.K1), "s"(p.K2), "s"(p.wsp_nct), "s"(p.pair_n),
+                 "s"((int)p.x1_blk), "s"((int)p.x2_blk), "s"(p.x1_div));
+    asm volatile("" ::"s"(p.ntype4[0]), "s"(p.ntype4[1]), "s"(p.ntype4[2]), "s"(p.ntype4[3]), "s"(p.ntype4[4]), "s"(p.ntype4[5]),
+                 "s"(p.ntype4[6]), "s"(p.ntype4[7]), "s"(p.ntype4[8]), "s"(p.ntype4[9]), "s"(p.ntype4[10]), "s"(p.ntype4[11]),
+                 "s"(p.ntype4[12]), "s"(p.ntype4[13]), "s"(p.ntype4[14]), "s"(p.ntype4[15]));
+}
+
 template <bool RMS, int PREC, bool ROWMAJOR, int PF = 8>  // PF: chunks in flight
-__global__ __launch_bounds__(256) void k_gl4y(const GLArgs p, int ntile_c, int64_t ntile_r, const YOut yo) {
+__global__ __launch_bounds__(256) void k_gl4y(const GL4GArgs p) {
+    gl4g_preload(p);
     const int lane = threadIdx.x & 63, l32 = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t u = (int64_t)blockIdx.x * 4 + wave;
-    const int tc = (int)(u % ntile_c);
-    const int64_t rj = u / ntile_c;
+    // unit = (row tile, node, column tile), column tile fastest (sd_gl4_args.h: no division)
+    const Unit3 un = decode_unit(blockIdx.x * 4u + (uint32_t)wave, p.da, p.db);
+    const int tc = (int)un.lo, j = (int)un.mid;
+    const int64_t tr = un.hi;
     const int J = p.J;
-    const int j = (int)(rj % J);
-    const int64_t tr = rj / J;
-    if (tr >= ntile_r) return;  // wave-uniform
+    if (tr >= p.ntile_r) return;  // wave-uniform
+    const int jt = gl4_node_type(p, j);  // wave-uniform
     const int64_t row0 = tr * 32;
     const int K = p.K1 + p.K2;
     const int nchunk = K >> 4;
@@ -283,7 +306,7 @@ __global__ __launch_bounds__(256) void k_gl4y(const GLArgs p, int ntile_c, int64
                                 : p.x1 + ((ac + p.x1_row0) / p.x1_div) * p.x1_rs + (int64_t)j * p.K1 + 8 * h;
     const float* x2r = !p.K2 ? nullptr
                              : p.x2_blk ? p.x2 + blk_off(arow, j, 8 * h, J, p.K2) : p.x2 + ac * p.x2_rs + (int64_t)j * p.K2 + 8 * h;
-    const _Float16* wbase = p.wsp + ((int64_t)p.ntype[j] * nchunk * p.wsp_nct + tc) * 1024 + lane * 8;
+    const _Float16* wbase = p.wsp + ((int64_t)jt * nchunk * p.wsp_nct + tc) * 1024 + lane * 8;
     const int64_t wcs = (int64_t)p.wsp_nct * 1024;  // halves per chunk
 
     floatx4 xa[PF], xb[PF];
@@ -332,7 +355,7 @@ __global__ __launch_bounds__(256) void k_gl4y(const GLArgs p, int ntile_c, int64
     // the bias before the operand loads: loaded after the K loop it was the youngest memory op, and
     // its vmcnt(0) put one more memory latency between the last MFMA and the stores
     const int ncol = tc * 32 + l32;
-    const float bv = (p.bias && ncol < p.N) ? p.bias[p.wrow[j] + ncol] : 0.f;
+    const float bv = (p.bias && ncol < p.N) ? p.bias[jt * p.N + ncol] : 0.f;
 #pragma unroll
     for (int i = 0; i < PF; ++i) issue(i, i);
     for (int c0 = 0; c0 < nchunk - PF; c0 += PF) {
@@ -361,15 +384,16 @@ __global__ __launch_bounds__(256) void k_gl4y(const GLArgs p, int ntile_c, int64
     auto store = [&](const floatx16& v) {
         if constexpr (ROWMAJOR) {
             if (ncol < p.N) {
-                float* y = yo.y + tr * yo.y_ts + j * yo.y_js + tc * yo.y_cs + l32;
+                float* y = p.y + tr * p.y_ts + (int64_t)j * p.y_js + (int64_t)tc * p.y_cs + l32;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int rr = (r & 3) + 8 * (r >> 2) + 4 * h;
-                    if (row0 + rr < p.B) y[rr * yo.y_rs] = v[r] * sc[r] + bv;
+                    if (row0 + rr < p.B) y[(int64_t)rr * p.y_rs] = v[r] * sc[r] + bv;
                 }
             }
-        } else {  // the split route's column-tiled scratch: every row of the tile, N % 32 == 0
-            float* y = p.zs + zs_off(row0, j, tc * 32, J, p.N) + l32;
+        } else {  // the split route's column-tiled scratch (zs_off through the strides: y_rs = 32): every
+                  // row of the tile, N % 32 == 0
+            float* y = p.y + tr * p.y_ts + (int64_t)j * p.y_js + (int64_t)tc * p.y_cs + l32;
 #pragma unroll
             for (int r = 0; r < 16; ++r) y[((r & 3) + 8 * (r >> 2) + 4 * h) << 5] = v[r] * sc[r] + bv;
         }
@@ -379,7 +403,8 @@ __global__ __launch_bounds__(256) void k_gl4y(const GLArgs p, int ntile_c, int64
     // addresses: program order); after the stores, so no accumulator is live across the call
     if (oor) {
         if (p.status && lane == 0) atomicOr(p.status, 1u);
-        store(exact_tile_f32(p, row0, j, tc * 32));
+        store(exact_tile_f32_impl(p.x1, p.x1_rs, p.K1, p.x1_div, p.x1_row0, p.x1_blk, p.x2, p.x2_rs, p.K2, p.x2_blk, p.B, p.J,
+                                  p.W, jt * p.N, p.N, p.wsp_unscale, row0, j, tc * 32));
     }
 }
 
@@ -424,8 +449,7 @@ __device__ __forceinline__ void g4_async(floatx4& d, const float* p) {
 // The workgroup's work: unit u = (node j, row group, column group); smem_raw = its
 // gl4t_smem_bytes of LDS.  A row group is NWV waves x RT 32-row tiles.
 template <bool RMS, int PREC, int CT, int NCH, bool ROWMAJOR, int RT, int PF>
-__device__ __forceinline__ void gl4t_body(const GLArgs& p, int ncg, int64_t ntile_r, const YOut& yo, const int64_t u,
-                                          const int tid, char* __restrict__ smem_raw) {
+__device__ __forceinline__ void gl4t_body(const GL4GArgs& p, const Unit3 un, const int tid, char* __restrict__ smem_raw) {
     static_assert(PREC != 2 || RT == 1, "bf16 operands: one row tile per wave");
     static_assert(PF >= 2 && PF <= 4, "chunks in flight");
     constexpr int NWV = 4;                      // waves per workgroup
@@ -443,14 +467,16 @@ __device__ __forceinline__ void gl4t_body(const GLArgs& p, int ncg, int64_t ntil
     // groups, then nodes, so an XCD's contiguous share of u holds one or two nodes' weights
     // (N = 768: 5.9 MB of split weights for all 10 types did not fit a 4 MB L2 when every XCD
     // walked every node: 196 MB fetched per launch for ~45 MB of operands)
-    const int cg = (int)(u % ncg);
+    // (decode_unit, sd_gl4_args.h: multiply-high by the host's reciprocals, no division)
+    const int cg = (int)un.lo, ncg = (int)p.da.d;
+    const int64_t ntile_r = p.ntile_r;
     // a paired launch (GLArgs::pair_n): the upper half of the column groups is the second layer,
     // with its own weight scale (the f16 hi / lo values depend on it)
     const bool second = p.pair_n && 2 * cg >= ncg;  // workgroup-uniform
     const float unscale = second ? p.wsp_unscale2 : p.wsp_unscale;
-    const int64_t nrg = (ntile_r + NWV * RT - 1) / (NWV * RT);
-    const int j = (int)((u / ncg) / nrg);
-    const int64_t rgi = (u / ncg) % nrg;
+    const int j = (int)un.hi;
+    const int jt = gl4_node_type(p, j);  // workgroup-uniform
+    const int64_t rgi = un.mid;
     const int64_t tr0 = (rgi * NWV + wave) * RT;  // this wave's first 32-row tile
     // per row tile: its rows (a dead tile -- past the batch -- reads tile 0 and stores nothing)
     int64_t row0[RT], arow[RT];
@@ -494,8 +520,8 @@ __device__ __forceinline__ void gl4t_body(const GLArgs& p, int ncg, int64_t ntil
     // serial memory round trips in the store tail
     float bvp[CT];
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct) bvp[ct] = p.bias ? p.bias[p.wrow[j] + (cg * CT + ct) * 32 + l32] : 0.f;
-    const _Float16* wt0 = p.wsp + ((int64_t)p.ntype[j] * NCH * p.wsp_nct + cg * CT) * 1024;
+    for (int ct = 0; ct < CT; ++ct) bvp[ct] = p.bias ? p.bias[jt * p.N + (cg * CT + ct) * 32 + l32] : 0.f;
+    const _Float16* wt0 = p.wsp + ((int64_t)jt * NCH * p.wsp_nct + cg * CT) * 1024;
     // Pieces of wave w per chunk: q0 = 64 w + NT k < CT * PPT (two counts, wave-uniform).
     constexpr int NPC = CT * PPT;
     constexpr int XL = 2 * RT;  // x loads per chunk and lane
@@ -664,7 +690,7 @@ __device__ __forceinline__ void gl4t_body(const GLArgs& p, int ncg, int64_t ntil
                 sc[r] *= 1.0f / fmaxf(sqrtf(n2), 1e-12f);
             }
         }
-        float* y = yo.y + tr * yo.y_ts + j * yo.y_js + (int64_t)cg * CT * yo.y_cs;  // YOut as k_gl4y's
+        float* y = p.y + tr * p.y_ts + (int64_t)j * p.y_js + (int64_t)cg * CT * p.y_cs;  // as k_gl4y's
         auto store_tile = [&](int ct, const floatx16& v, float bv) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) sT[((r & 3) + 8 * (r >> 2) + 4 * h) * TS + l32] = v[r] * sc[r] + bv;
@@ -674,7 +700,7 @@ __device__ __forceinline__ void gl4t_body(const GLArgs& p, int ncg, int64_t ntil
                 const int row = 8 * q + (lane >> 3), c4 = (lane & 7) * 4;
                 const floatx4 o = *reinterpret_cast<const floatx4*>(sT + row * TS + c4);
                 if (!ROWMAJOR || row0[rt] + row < p.B)  // row-major z holds rows < B only
-                    *reinterpret_cast<floatx4*>(y + (int64_t)row * yo.y_rs + ct * yo.y_cs + c4) = o;
+                    *reinterpret_cast<floatx4*>(y + (int64_t)row * p.y_rs + (int64_t)ct * p.y_cs + c4) = o;
             }
             __builtin_amdgcn_wave_barrier();
         };
@@ -690,22 +716,23 @@ __device__ __forceinline__ void gl4t_body(const GLArgs& p, int ncg, int64_t ntil
                 // (a paired launch: the tile's own layer -- its f32 weights, pair_n columns, its scale)
                 const floatx16 ex = exact_tile_f32_impl(p.x1, p.x1_rs, p.K1, p.x1_div, p.x1_row0, p.x1_blk, p.x2, p.x2_rs, p.K2,
                                                         p.x2_blk, p.B, p.J, second ? p.W2 : p.W,
-                                                        p.pair_n ? p.wrow[j] >> 1 : p.wrow[j], p.pair_n ? p.pair_n : p.N,
+                                                        jt * (p.pair_n ? p.pair_n : p.N), p.pair_n ? p.pair_n : p.N,
                                                         unscale, row0[rt], j, second ? col - p.pair_n : col);
-                store_tile(ct, ex, p.bias ? p.bias[p.wrow[j] + col + l32] : 0.f);
+                store_tile(ct, ex, p.bias ? p.bias[jt * p.N + col + l32] : 0.f);
             }
         }
     }
 }
 
 template <bool RMS, int PREC, int CT, int NCH, bool ROWMAJOR, int RT, int PF>
-__global__ __launch_bounds__(256, 2) void k_gl4t(const GLArgs p, int ncg, int64_t ntile_r, const YOut yo) {
+__global__ __launch_bounds__(256, 2) void k_gl4t(const GLArgs, int, int64_t, const YOut yo) {
     __shared__ __attribute__((aligned(16))) char smem_raw[gl4t_smem_bytes<PREC, CT, NCH, PF>()];
     // XCD-aware order (k_gl4's): consecutive u -- the column groups of one (row group, node), which
     // read the same x -- on one XCD (blocks b, b + 8, ... share one), so x reaches that L2 once
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int64_t u = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-    gl4t_body<RMS, PREC, CT, NCH, ROWMAJOR, RT, PF>(p, ncg, ntile_r, yo, u, threadIdx.x, smem_raw);
+    const GL4GArgs& p = yo.g;
+    gl4g_preload(p);
+    const Unit3 un = decode_unit(xcd_remap(blockIdx.x, p.q8, p.r8), p.da, p.db);
+    gl4t_body<RMS, PREC, CT, NCH, ROWMAJOR, RT, PF>(p, un, threadIdx.x, smem_raw);
 }
 
 // Epilogue of the fused to_qkv + Attention kernel (MODE 1), J <= 32, dh = 32, 8 waves, a
@@ -713,8 +740,8 @@ __global__ __launch_bounds__(256, 2) void k_gl4t(const GLArgs p, int ncg, int64_
 // then wave w runs the attention of row 8*slab + w exactly as k_attention<JT> does (same f32 MFMA
 // order over JT 16-node tiles, expf softmax), writing out[row][n][head*32 + d].
 // FROM_YS (MODE 3, split route phase 2): k_gl4 MODE 3 has put slab q8only in sY already.
-template <int J, int NW, int NPW, bool FROM_YS = false>
-__device__ __forceinline__ void attention_epilogue(const GLArgs& p, floatx16 (&acc)[NPW][1][3], float* smem,
+template <int J, int NW, int NPW, bool FROM_YS = false, class A = GLArgs>  // A: GLArgs, or MODE 3's GL4MArgs
+__device__ __forceinline__ void attention_epilogue(const A& p, floatx16 (&acc)[NPW][1][3], float* smem,
                                                    const float* sG, int64_t row0, int head, int wave, int lane,
                                                    int q8only = 0) {
     constexpr int COLS = 96;
@@ -939,8 +966,10 @@ __device__ __forceinline__ void node_layernorm(floatx4 (&z)[IB], const float* __
 //   (global_load_dwordx4 a chunk ahead, ds_write_b128 after the chunk's MFMAs).
 // The workgroup's work for virtual block index bx of a grid of nwg (k_gl4 passes blockIdx.x /
 // gridDim.x); smem = its dynamic LDS.
-template <int J, int NW, int RT, int CT, bool RMS, int MODE = 0, int PREC = 0, int STG = 0>
-__device__ __forceinline__ void gl4_body(const GLArgs& p, const int bx, const int nwg, float* __restrict__ smem) {
+// A: the argument block -- GLArgs for the one-kernel tiles (MODE 0 / 1), the compact GL4MArgs for the
+// split route's mixing phase (MODE 2 / 3: sd_gl4_args.h)
+template <int J, int NW, int RT, int CT, bool RMS, int MODE = 0, int PREC = 0, int STG = 0, class A = GLArgs>
+__device__ __forceinline__ void gl4_body(const A& p, const int bx, const int nwg, float* __restrict__ smem) {
     static_assert(MODE == 0 || MODE == 2 || (CT == 3 && RT == 1 && J <= 32 && NW == 8), "attention mode: 32 x (q|k|v)");
     static_assert(MODE < 2 || (RT == 1 && STG == 0), "split-route phase 2: one 32-row tile");
     constexpr bool PH2 = MODE == 2 || MODE == 3;  // split-route phase 2: Y from the scratch, no K loop
@@ -956,7 +985,8 @@ __device__ __forceinline__ void gl4_body(const GLArgs& p, const int bx, const in
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l32 = lane & 31, h = lane >> 5, lr = lane & 15, lg = lane >> 4;
     constexpr int TILE_H = PREC ? 512 : 1024;   // halves of one 32-column tile per k chunk (hi | hi+lo)
-    const int stage_h = MODE >= 2 ? 0 : p.ntypes * CT * TILE_H;  // halves per weight stage
+    int stage_h = 0;  // halves per weight stage
+    if constexpr (MODE < 2) stage_h = p.ntypes * CT * TILE_H;
     const int wfl = stage_h;                   // two stages of halves = stage_h floats
     constexpr bool ATT = MODE == 1 || MODE == 3;
     // Y slab (+ Z rows; MODE 3: Z overwrites Y, attention_epilogue<…, FROM_YS>)
@@ -967,40 +997,49 @@ __device__ __forceinline__ void gl4_body(const GLArgs& p, const int bx, const in
     float* sG = smem + (wfl > yfl ? wfl : yfl);
     float* sF = sG + J * J;  // FiLM (scale + 1 | shift) for this workgroup's columns
 
-    const int ntile_c = ATT ? p.attn_heads : (p.N + COLS - 1) / COLS;
     const int xcd = bx & 7, q8 = nwg >> 3, r8 = nwg & 7;
     // XCD-aware order: consecutive L (the column tiles of one row tile) on one XCD, so x is
     // fetched into that XCD's L2 once.  attn_order 1 (fused attention): L = blockIdx, i.e. head
     // h = blockIdx % heads runs on XCD h % 8 and each XCD's L2 keeps only its heads' weights.
     // Split-route phase 2: workgroup = (tile, 16-row slab) in MODE 2, (tile, 8-row slab) in MODE 3.
-    const int L = MODE == 2   ? (int)(bx >> 1)
-                  : MODE == 3 ? (int)(bx >> 2)
-                  : (MODE == 1 && p.attn_order == 1)
-                      ? (int)bx
-                      : (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bx >> 3);
+    int L, ctile;
+    int64_t row0;
     const int slab = MODE == 2 ? (int)(bx & 1) : MODE == 3 ? (int)(bx & 3) : 0;
-    const int ctile = L % ntile_c;
-    const int64_t row0 = (int64_t)(L / ntile_c) * (32 * RT);
+    int nchunk = 0;
+    if constexpr (PH2) {  // (tile, column tile) by the host's reciprocal (fast_divmod): no division
+        L = MODE == 2 ? (int)(bx >> 1) : (int)(bx >> 2);
+        uint32_t q, r;
+        fast_divmod((uint32_t)L, p.ntc, q, r);
+        ctile = (int)r;
+        row0 = (int64_t)q * 32;
+        (void)xcd; (void)q8; (void)r8;
+    } else {
+        const int ntile_c = ATT ? p.attn_heads : (p.N + COLS - 1) / COLS;
+        L = (MODE == 1 && p.attn_order == 1) ? (int)bx : (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bx >> 3);
+        ctile = L % ntile_c;
+        row0 = (int64_t)(L / ntile_c) * (32 * RT);
+        nchunk = (p.K1 + p.K2) >> 4;  // even (checked at launch)
+    }
     const int c0 = ctile * COLS;
-    const int K = p.K1 + p.K2;
-    const int nchunk = K >> 4;  // even (checked at launch)
 
     // x row pointers: row-major (B, J, K) with the tail rows clamped to row 0 (never stored), or
     // row-blocked (padded to 32 rows: read as they are) -- see blk_off
     const float* x1r[RT];
     const float* x2r[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-        const int64_t arow = row0 + 32 * rt + l32;
-        const int64_t ac = arow < p.B ? arow : 0;
-        x1r[rt] = p.x1_blk ? p.x1 + blk_off(arow, 0, 8 * h, J, p.K1) : p.x1 + ((ac + p.x1_row0) / p.x1_div) * p.x1_rs + 8 * h;
-        x2r[rt] = !p.K2 ? nullptr : p.x2_blk ? p.x2 + blk_off(arow, 0, 8 * h, J, p.K2) : p.x2 + ac * p.x2_rs + 8 * h;
-    }
     int jn[NPW], toff[NPW];  // wave-uniform (SGPR): clamped node, its type's stage offset
+    if constexpr (!PH2) {
 #pragma unroll
-    for (int m = 0; m < NPW; ++m) {
-        jn[m] = min(wave + NW * m, J - 1);
-        toff[m] = p.ntype[jn[m]] * (CT * TILE_H);
+        for (int rt = 0; rt < RT; ++rt) {
+            const int64_t arow = row0 + 32 * rt + l32;
+            const int64_t ac = arow < p.B ? arow : 0;
+            x1r[rt] = p.x1_blk ? p.x1 + blk_off(arow, 0, 8 * h, J, p.K1) : p.x1 + ((ac + p.x1_row0) / p.x1_div) * p.x1_rs + 8 * h;
+            x2r[rt] = !p.K2 ? nullptr : p.x2_blk ? p.x2 + blk_off(arow, 0, 8 * h, J, p.K2) : p.x2 + ac * p.x2_rs + 8 * h;
+        }
+#pragma unroll
+        for (int m = 0; m < NPW; ++m) {
+            jn[m] = min(wave + NW * m, J - 1);
+            toff[m] = p.ntype[jn[m]] * (CT * TILE_H);
+        }
     }
 
     // (mixing-epilogue helpers, defined before the phase-2 loads so MODE 2 can issue its residual
@@ -1073,7 +1112,7 @@ __device__ __forceinline__ void gl4_body(const GLArgs& p, const int bx, const in
                 const int cc = (q % C4) * 4, r = (q / C4) & 15, j = q / (16 * C4);
                 dst = sY + j * YS + r * YR + cc;
                 // (a paired launch: this layer's columns of the wider scratch, GLArgs::zs_n / zs_c0)
-                return p.zs + zs_off(row0 + 16 * slab + r, j, p.zs_c0 + c0 + cc, J, p.zs_n ? p.zs_n : p.N);
+                return p.zs + zs_off(row0 + 16 * slab + r, j, p.zs_c0 + c0 + cc, J, p.zs_n);
             } else {
                 const int cc = (q & 7) * 4, rr = (q >> 3) & 7, j = (q >> 6) % J, ct = (q >> 6) / J;
                 dst = sY + j * YS8 + rr * COLS + 32 * ct + cc;
@@ -1502,13 +1541,22 @@ __global__ __launch_bounds__(NW * 64, 1) void k_gl4(const GLArgs p) {
 // residual and output -- and runs that layer's own MODE 2 body on the block index it has in a
 // launch of its own.
 template <int J, int PREC>
-__global__ __launch_bounds__(512, 1) void k_gl4_pair(const GLArgs a, const GLArgs b) {
+__global__ __launch_bounds__(512, 1) void k_gl4_pair(const GL4PairArgs pp) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int nta = a.N >> 5, ntb = b.N >> 5;
-    const int L = blockIdx.x >> 1, slab = blockIdx.x & 1;
-    const int pt = L % (nta + ntb), tr = L / (nta + ntb);
-    if (pt < nta) gl4_body<J, 8, 1, 1, false, 2, PREC, 0>(a, ((tr * nta + pt) << 1) | slab, gridDim.x, smem);
-    else gl4_body<J, 8, 1, 1, false, 2, PREC, 0>(b, ((tr * ntb + pt - nta) << 1) | slab, gridDim.x, smem);
+    const uint32_t nta = pp.nta, ntb = pp.nt.d - pp.nta;
+    const uint32_t slab = blockIdx.x & 1;
+    uint32_t pt, tr;
+    fast_divmod(blockIdx.x >> 1, pp.nt, tr, pt);
+    if (pt < nta) gl4_body<J, 8, 1, 1, false, 2, PREC, 0>(pp.a, (int)(((tr * nta + pt) << 1) | slab), 0, smem);
+    else gl4_body<J, 8, 1, 1, false, 2, PREC, 0>(pp.b, (int)(((tr * ntb + pt - nta) << 1) | slab), 0, smem);
+}
+
+// The split route's mixing phase as a kernel of its own: MODE 2 (one 32-column tile) / MODE 3 (a head's
+// q | k | v tiles) of gl4_body on the compact argument block
+template <int J, int MODE, int PREC>
+__global__ __launch_bounds__(512, 1) void k_gl4m(const GL4MArgs p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    gl4_body<J, 8, 1, MODE == 3 ? 3 : 1, false, MODE, PREC, 0>(p, blockIdx.x, 0, smem);
 }
 
 // v4 weight staging (GLArgs::gl4_stage): 0 = LDS-DMA stages, 1 = register-staged stages (2, a
@@ -1544,14 +1592,29 @@ static hipError_t gl4_launch_t(const GLArgs& a, bool rms, hipStream_t s) {
     // Every launch takes exactly the LDS it uses and may share its CU with other kernels' workgroups
     // (row chains, concurrent plans): the co-residency hazard of rounds 1-2 was the packed-FP32
     // instructions of the co-resident update kernel, not these tiles (build.py).
-    auto kt = rms ? k_gl4<J, NW, RT, CT, true, MODE, PREC, STG> : k_gl4<J, NW, RT, CT, false, MODE, PREC, STG>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
+    if constexpr (MODE >= 2) {  // the split route's mixing phase: its own compact argument block
+        static_assert(NW == 8 && RT == 1 && STG == 0 && CT == (MODE == 3 ? 3 : 1), "k_gl4m's tile");
+        GL4MArgs m;
+        if (rms || !gl4_grid_ok((int64_t)ntile_c * ntile_r * (MODE == 2 ? 2 : 4)) || !pack_gl4m(a, (uint32_t)ntile_c, &m))
+            return hipErrorInvalidValue;
+        auto km = k_gl4m<J, MODE, PREC>;
+        if (lds > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute((const void*)km, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+        }
+        g_route_bits |= kRouteMixPhase;
+        hipLaunchKernelGGL(km, grid, dim3(NW * 64), lds, s, m);
+        return hipGetLastError();
+    } else {
+        auto kt = rms ? k_gl4<J, NW, RT, CT, true, MODE, PREC, STG> : k_gl4<J, NW, RT, CT, false, MODE, PREC, STG>;
+        if (lds > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute((const void*)kt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+        }
+        g_route_bits |= MODE == 1 ? kRouteFusedAttn : kRouteOneKernel;
+        hipLaunchKernelGGL(kt, grid, dim3(NW * 64), lds, s, a);
+        return hipGetLastError();
     }
-    g_route_bits |= MODE >= 2 ? kRouteMixPhase : MODE == 1 ? kRouteFusedAttn : kRouteOneKernel;
-    hipLaunchKernelGGL(kt, grid, dim3(NW * 64), lds, s, a);
-    return hipGetLastError();
 }
 
 // ---- split route (small grids) -------------------------------------------------
@@ -1605,40 +1668,44 @@ int graph_linear_split_route(const GLArgs& a) {
 }
 
 template <bool ROWMAJOR, int PF>
-static void launch_gl4y_pf(const GLArgs& a, bool rms, int ntc, int64_t ntile_r, const YOut& yo, dim3 grid, hipStream_t s) {
-    if (a.prec == 1) {
-        if (rms) hipLaunchKernelGGL((k_gl4y<true, 1, ROWMAJOR, PF>), grid, dim3(256), 0, s, a, ntc, ntile_r, yo);
-        else hipLaunchKernelGGL((k_gl4y<false, 1, ROWMAJOR, PF>), grid, dim3(256), 0, s, a, ntc, ntile_r, yo);
+static void launch_gl4y_pf(const GL4GArgs& g, int prec, bool rms, dim3 grid, hipStream_t s) {
+    if (prec == 1) {
+        if (rms) hipLaunchKernelGGL((k_gl4y<true, 1, ROWMAJOR, PF>), grid, dim3(256), 0, s, g);
+        else hipLaunchKernelGGL((k_gl4y<false, 1, ROWMAJOR, PF>), grid, dim3(256), 0, s, g);
     } else {
-        if (rms) hipLaunchKernelGGL((k_gl4y<true, 0, ROWMAJOR, PF>), grid, dim3(256), 0, s, a, ntc, ntile_r, yo);
-        else hipLaunchKernelGGL((k_gl4y<false, 0, ROWMAJOR, PF>), grid, dim3(256), 0, s, a, ntc, ntile_r, yo);
+        if (rms) hipLaunchKernelGGL((k_gl4y<true, 0, ROWMAJOR, PF>), grid, dim3(256), 0, s, g);
+        else hipLaunchKernelGGL((k_gl4y<false, 0, ROWMAJOR, PF>), grid, dim3(256), 0, s, g);
     }
 }
 
 template <bool ROWMAJOR>
-static hipError_t launch_gl4y(const GLArgs& a, bool rms, int ntc, int64_t ntile_r, const YOut& yo, hipStream_t s) {
+static hipError_t launch_gl4y(const GLArgs& a, bool rms, int ntc, int64_t ntile_r, const YDst& yo, hipStream_t s) {
     const int64_t units = ntile_r * a.J * ntc;
+    if (!gl4_grid_ok(units + 3)) return hipErrorInvalidValue;  // the unit decode is 32-bit
     const dim3 grid((unsigned)((units + 3) / 4));
     // any chunk count: the v5 GEMM phase (launch_gemm_split) passes K = 16 / 48 (odd nchunk) too
     const int nchunk = (a.K1 + a.K2) / 16;
     if (nchunk < 1 || (a.K1 + a.K2) % 16) return hipErrorNotSupported;
+    GL4GArgs g;  // unit = (row tile, node, column tile)
+    if (!pack_gl4g(a, ntile_r, yo.y, yo.y_rs, yo.y_js, yo.y_ts, yo.y_cs, (uint32_t)ntc, (uint32_t)a.J, grid.x, &g))
+        return hipErrorInvalidValue;
     g_route_bits |= kRouteGemmWave;
     // chunks in flight: a divisor of nchunk (the K loop's rounds: the loop issues unconditionally,
     // so PF must divide nchunk); every chunk of a K = 192 layer in flight on grids of at most one
     // workgroup per CU (the wave pays one memory latency per launch)
     if (grid.x <= 256 && a.prec == 0 && nchunk % 12 == 0)
-        launch_gl4y_pf<ROWMAJOR, 12>(a, rms, ntc, ntile_r, yo, grid, s);
-    else if (nchunk % 8 == 0) launch_gl4y_pf<ROWMAJOR, 8>(a, rms, ntc, ntile_r, yo, grid, s);
-    else if (nchunk % 6 == 0) launch_gl4y_pf<ROWMAJOR, 6>(a, rms, ntc, ntile_r, yo, grid, s);
-    else if (nchunk % 4 == 0) launch_gl4y_pf<ROWMAJOR, 4>(a, rms, ntc, ntile_r, yo, grid, s);
-    else if (nchunk % 3 == 0) launch_gl4y_pf<ROWMAJOR, 3>(a, rms, ntc, ntile_r, yo, grid, s);
-    else if (nchunk % 2 == 0) launch_gl4y_pf<ROWMAJOR, 2>(a, rms, ntc, ntile_r, yo, grid, s);
-    else launch_gl4y_pf<ROWMAJOR, 1>(a, rms, ntc, ntile_r, yo, grid, s);
+        launch_gl4y_pf<ROWMAJOR, 12>(g, a.prec, rms, grid, s);
+    else if (nchunk % 8 == 0) launch_gl4y_pf<ROWMAJOR, 8>(g, a.prec, rms, grid, s);
+    else if (nchunk % 6 == 0) launch_gl4y_pf<ROWMAJOR, 6>(g, a.prec, rms, grid, s);
+    else if (nchunk % 4 == 0) launch_gl4y_pf<ROWMAJOR, 4>(g, a.prec, rms, grid, s);
+    else if (nchunk % 3 == 0) launch_gl4y_pf<ROWMAJOR, 3>(g, a.prec, rms, grid, s);
+    else if (nchunk % 2 == 0) launch_gl4y_pf<ROWMAJOR, 2>(g, a.prec, rms, grid, s);
+    else launch_gl4y_pf<ROWMAJOR, 1>(g, a.prec, rms, grid, s);
     return hipGetLastError();
 }
 
 template <bool ROWMAJOR>
-static hipError_t launch_gl4t(const GLArgs& a, bool rms, int64_t ntile_r, const YOut& yo, hipStream_t s);
+static hipError_t launch_gl4t(const GLArgs& a, bool rms, int64_t ntile_r, const YDst& yo, hipStream_t s);
 
 // v5's GEMM phase on split-f16 products (J > 21; sd_graph_linear_v5.hip): z[b, j, n] row-major
 // with row stride z_rs, rows < B only.  hipErrorNotSupported without split weights.
@@ -1646,7 +1713,7 @@ hipError_t launch_gemm_split(const GLArgs& a, bool rms, float* z, int64_t z_rs, 
     if (!a.wsp || a.prec == 2 || (a.K1 + a.K2) % 16 || a.K1 % 16 || a.x1_blk || a.x2_blk) return hipErrorNotSupported;
     const int64_t ntile_r = (a.B + 31) / 32;
     const int ntc = (a.N + 31) / 32;
-    const YOut yo{z, z_rs, a.N, 32 * z_rs, 32};
+    const YDst yo{z, z_rs, a.N, 32 * z_rs, 32};
     // the tiled phase (128 rows x up to 192 columns of one node per workgroup) where the shape
     // has one
     if (((uintptr_t)z & 15) == 0 && (z_rs & 3) == 0 && (a.N & 3) == 0) {  // 16-B Y pieces
@@ -1657,16 +1724,21 @@ hipError_t launch_gemm_split(const GLArgs& a, bool rms, float* z, int64_t z_rs, 
 }
 
 template <int CT, int NCH, bool ROWMAJOR, int RT, int PF = 2>
-static hipError_t launch_gl4t_v(const GLArgs& a, bool rms, int64_t ntile_r, const YOut& yo, hipStream_t s) {
+static hipError_t launch_gl4t_v(const GLArgs& a, bool rms, int64_t ntile_r, const YDst& yo, hipStream_t s) {
     const int ncg = a.N / (32 * CT);  // column groups
-    const dim3 grid((unsigned)(((ntile_r + 4 * RT - 1) / (4 * RT)) * a.J * ncg)), block(256);
+    const int64_t nrg = (ntile_r + 4 * RT - 1) / (4 * RT);  // row groups: 4 waves x RT 32-row tiles
+    if (ncg < 1 || !gl4_grid_ok(nrg * a.J * ncg)) return hipErrorInvalidValue;  // the unit decode is 32-bit
+    const dim3 grid((unsigned)(nrg * a.J * ncg)), block(256);
+    YOut yd;  // unit = (node, row group, column group), column group fastest
+    if (!pack_gl4g(a, ntile_r, yo.y, yo.y_rs, yo.y_js, yo.y_ts, yo.y_cs, (uint32_t)ncg, (uint32_t)nrg, grid.x, &yd.g))
+        return hipErrorInvalidValue;
     auto kt = a.prec == 1 ? (rms ? k_gl4t<true, 1, CT, NCH, ROWMAJOR, RT, PF> : k_gl4t<false, 1, CT, NCH, ROWMAJOR, RT, PF>)
                           : (rms ? k_gl4t<true, 0, CT, NCH, ROWMAJOR, RT, PF> : k_gl4t<false, 0, CT, NCH, ROWMAJOR, RT, PF>);
     if constexpr (!ROWMAJOR && RT == 1) {  // bf16 mode (precision 2): the split route's scratch output only
         if (a.prec == 2) kt = rms ? k_gl4t<true, 2, CT, NCH, false, 1, 2> : k_gl4t<false, 2, CT, NCH, false, 1, 2>;
     }
     g_route_bits |= kRouteGemmTiled;
-    hipLaunchKernelGGL(kt, grid, block, 0, s, a, ncg, ntile_r, yo);
+    hipLaunchKernelGGL(kt, grid, block, 0, s, a, ncg, ntile_r, yd);
     return hipGetLastError();
 }
 
@@ -1680,7 +1752,7 @@ static hipError_t launch_gl4t_v(const GLArgs& a, bool rms, int64_t ntile_r, cons
 // (config 2 16,104 / 16,353 vs 16,498 / 16,375: its 72 KiB workgroups leave less room for the other
 // row chains' kernels), profiles/r04_ab/gl4t_ct8.txt
 template <bool ROWMAJOR>
-static hipError_t launch_gl4t(const GLArgs& a, bool rms, int64_t ntile_r, const YOut& yo, hipStream_t s) {
+static hipError_t launch_gl4t(const GLArgs& a, bool rms, int64_t ntile_r, const YDst& yo, hipStream_t s) {
     const int K = a.K1 + a.K2;
     if (a.K1 % 16 || (a.x1_div != 1 && a.x1_blk)) return hipErrorNotSupported;
     if (ROWMAJOR && a.N % 256 == 0 && K == 192 && a.prec != 2) return launch_gl4t_v<8, 12, ROWMAJOR, 1>(a, rms, ntile_r, yo, s);
@@ -1712,7 +1784,7 @@ template <int J>
 static hipError_t gl4_split(const GLArgs& a, bool rms, bool attn, int route, hipStream_t s) {
     const int64_t ntile_r = (a.B + 31) / 32;
     const int ntc = a.N / 32;
-    const YOut yo{a.zs, 32, 1024, (int64_t)(a.N / 32) * J * 1024, (int64_t)J * 1024};  // column-tiled (zs_off)
+    const YDst yo{a.zs, 32, 1024, (int64_t)(a.N / 32) * J * 1024, (int64_t)J * 1024};  // column-tiled (zs_off)
     hipError_t e = route == 2 ? launch_gl4t<false>(a, rms, ntile_r, yo, s) : hipErrorNotSupported;
     if (e == hipErrorNotSupported) {
         if (a.prec == 2) return hipErrorNotSupported;  // k_gl4y has no bf16 form
@@ -1746,15 +1818,18 @@ static hipError_t gl4_split_dispatch(const GLArgs& a, bool rms, bool attn, int r
 template <int J>
 static hipError_t gl4_pair(const GLArgs& pr, const GLArgs& a, const GLArgs& b, hipStream_t s) {
     const int64_t ntile_r = (pr.B + 31) / 32;
-    const YOut yo{pr.zs, 32, 1024, (int64_t)(pr.N / 32) * J * 1024, (int64_t)J * 1024};  // as gl4_split, 2 N wide
+    const YDst yo{pr.zs, 32, 1024, (int64_t)(pr.N / 32) * J * 1024, (int64_t)J * 1024};  // as gl4_split, 2 N wide
     const hipError_t e = launch_gl4t<false>(pr, false, ntile_r, yo, s);
     if (e != hipSuccess) return e;
+    if (!gl4_grid_ok((int64_t)(a.N + b.N) / 32 * ntile_r * 2)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((a.N + b.N) / 32 * ntile_r * 2));
+    GL4PairArgs pp;
+    if (!pack_gl4_pair(a, b, &pp)) return hipErrorInvalidValue;
     const size_t lds = ((size_t)J * (16 * 36 + 16) + (size_t)J * J + 64) * sizeof(float);  // gl4_launch_t's MODE 2, CT = 1
     static_assert((J * (16 * 36 + 16) + J * J + 64) * sizeof(float) <= 64 * 1024, "default dynamic LDS");
     g_route_bits |= kRouteMixPhase;
-    if (pr.prec == 2) hipLaunchKernelGGL((k_gl4_pair<J, 2>), grid, dim3(512), lds, s, a, b);
-    else hipLaunchKernelGGL((k_gl4_pair<J, 0>), grid, dim3(512), lds, s, a, b);
+    if (pr.prec == 2) hipLaunchKernelGGL((k_gl4_pair<J, 2>), grid, dim3(512), lds, s, pp);
+    else hipLaunchKernelGGL((k_gl4_pair<J, 0>), grid, dim3(512), lds, s, pp);
     return hipGetLastError();
 }
 

@@ -38,6 +38,9 @@ def kind(name):
         return "gemm_wave"
     if "k_gl4_pair" in n:  # the mixing phase of two layers whose GEMM phase was one paired k_gl4t dispatch
         return "mix_pair"
+    m = re.match(r"sd::k_gl4m<(.*)>", n)  # <J, MODE, PREC>: the split route's mixing phase
+    if m:
+        return {2: "mix_phase", 3: "attn_phase"}.get(int(m.group(1).split(",")[1]), "other")
     m = re.match(r"sd::k_gl4<(.*)>", n)
     if m:
         args = m.group(1).split(",")
