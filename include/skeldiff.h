@@ -704,6 +704,30 @@ int sd_motion_draws(const int64_t* sample_idx, int64_t B, int32_t joints, int32_
                     void* stream);
 int32_t sd_motion_batch_frame_tile(int32_t joints);
 
+/* The forward process for k noisy copies of every training sequence: p_losses' repeat_interleave
+ * of x_start / t (src/core/diffusion/base.py:262-268), get_white_noise and q_sample (nonisotropic.py:152-159,
+ * isotropic.py q_sample) in one kernel.  x0 (nseq, J, D), t (nseq) i64, sqrt_alphas_cumprod (T); either
+ * M (T, J, J) = Umm_sqrt_Lambda_bar_t or, with M NULL, sqrt_one_minus_alphas_cumprod (T):
+ *   x_t[r, i, d] = sqrt_alphas_cumprod[t_s] x0[s, i, d] + sum_j M[t_s, i, j] eps[r, j, d]
+ *   x_t[r, i, d] = sqrt_alphas_cumprod[t_s] x0[s, i, d] + sqrt_one_minus_alphas_cumprod[t_s] eps[r, i, d]
+ * in f32, the products summed in this order by fused multiply-adds.
+ * Rows: with sel NULL x_t (and noise_out) hold nseq k rows in repeat_interleave order, r = s k + copy; with
+ * sel (nseq) i64 they hold nseq rows, the copy sel[s] of each sequence, bit for bit the rows s k + sel[s] of
+ * the full launch.
+ * Noise: with noise_in NULL, eps of a row comes from the sampler's Philox stream (sd_noise_fill) keyed
+ * (seed, row = row0 + s k + copy, step), quad q = elements 4 q .. 4 q + 3 of the row's J D values; otherwise
+ * noise_in (nseq k, J, D) is read at row s k + copy.  noise_out (optional, shaped like x_t) receives the eps
+ * that was used.
+ * All pointers are DEVICE memory, 16-byte aligned.  Checked on the host before any device call (SD_E_INVALID
+ * names the argument): NULL pointers, misaligned rows, nseq < 0, k < 1, J outside [1, 64], D outside [4, 256]
+ * or not a multiple of 4, T < 1, step outside [0, 2^31), row0 < 0, nseq k > 2^31 - 1, neither or both of M /
+ * sqrt_one_minus_alphas_cumprod.  nseq == 0: SD_OK, nothing launched.  t and sel cannot be checked on the
+ * host: the kernel clamps t to [0, T - 1] and sel to [0, k - 1], so neither becomes an out-of-bounds read. */
+int sd_q_sample_groups(const float* x0, const int64_t* t, const float* sqrt_alphas_cumprod, const float* M,
+                       const float* sqrt_one_minus_alphas_cumprod, int32_t T, int64_t nseq, int32_t k, int32_t J,
+                       int32_t D, const int64_t* sel, const float* noise_in, uint64_t seed, int64_t step, int64_t row0,
+                       float* x_t, float* noise_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

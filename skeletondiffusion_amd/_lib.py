@@ -48,6 +48,7 @@ EXPORTED = (
     "sd_gx_table_backward",
     "sd_optim_workspace_bytes", "sd_optim_grad_norm", "sd_optim_adam_step", "sd_optim_ema_update",
     "sd_motion_batch", "sd_motion_draws", "sd_motion_batch_frame_tile",
+    "sd_q_sample_groups",
 )
 
 # sd_plan_set_option keys (include/skeldiff.h)
@@ -214,6 +215,8 @@ def _declare(lib: ctypes.CDLL) -> None:
         "sd_motion_draws": (ctypes.c_int, [vp, i64, i32, i32, i64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                            ctypes.c_float, u64, i32, vp, vp, vp, vp, vp, vp]),
         "sd_motion_batch_frame_tile": (i32, [i32]),
+        "sd_q_sample_groups": (ctypes.c_int, [vp, vp, vp, vp, vp, i32, i64, i32, i32, i32, vp, vp, u64, i64, i64, vp, vp,
+                                              vp]),
         "sd_profile_step": (ctypes.c_int, [vp, vp, vp, i64, i32, i64, vp, sz, i32, ctypes.POINTER(ctypes.c_float),
                                            ctypes.POINTER(ctypes.c_int32), vp]),
     }

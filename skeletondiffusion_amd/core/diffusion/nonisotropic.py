@@ -157,7 +157,7 @@ class NonisotropicGaussianDiffusion(LatentDiffusion):
         """The Mahalanobis loss reduced per row.  On the device under autograd (fp32, J <= 64,
         F <= 256, loss_funct not overridden) it is one fused HIP kernel each way
         (training.mahalanobis_loss, sd_train.hip `k_mahalanobis`); otherwise loss_funct + mean."""
-        if (model_out.is_cuda and torch.is_grad_enabled() and model_out.dtype == torch.float32 and model_out.dim() == 3
+        if (model_out.is_cuda and _training.hip_gate() and model_out.dtype == torch.float32 and model_out.dim() == 3
                 and _training.hip_training_enabled() and type(self).loss_funct is NonisotropicGaussianDiffusion.loss_funct
                 and self.loss_reduction_type in ("l1", "mse") and self.objective in ("pred_noise", "pred_x0")
                 and model_out.shape[1] <= _training.MAX_NODES and model_out.shape[2] <= 256

@@ -206,7 +206,7 @@ def _hip_gru_sequence(cell: StaticGraphGRUCell, x: torch.Tensor, h0: torch.Tenso
     else:  # gx never changes: re-normalising an L1-normalised matrix is the identity
         if not cell.learn_influence:
             gx_last = cell.G
-        elif torch.is_grad_enabled():
+        elif _training.hip_gate():
             gx_last = _training.l1norm_rows(cell.G, 1e-12)
         else:
             gx_last = F.normalize(cell.G, p=1., dim=1)

@@ -82,7 +82,7 @@ class StaticGraphLinear(nn.Module):
 
     def hip_ghat_ok(self) -> bool:
         G = self.G
-        return (self.learn_influence and isinstance(G, torch.Tensor) and G.is_cuda and torch.is_grad_enabled()
+        return (self.learn_influence and isinstance(G, torch.Tensor) and G.is_cuda and _training.hip_gate()
                 and G.dtype == torch.float32 and _training.hip_training_enabled() and G.dim() == 2
                 and G.shape[0] == G.shape[1] <= _training.MAX_NODES)
 
@@ -93,7 +93,7 @@ class StaticGraphLinear(nn.Module):
         if pre is not None:  # set by Denoiser.forward: every G normalised in one launch
             return pre
         G = self.G
-        if (G.is_cuda and torch.is_grad_enabled() and G.dtype == torch.float32 and _training.hip_training_enabled()
+        if (G.is_cuda and _training.hip_gate() and G.dtype == torch.float32 and _training.hip_training_enabled()
                 and G.dim() == 2 and G.shape[0] == G.shape[1] <= _training.MAX_NODES):
             # training on the device: one HIP launch each way (sd_train.hip k_l1norm_rows)
             return _training.l1norm_rows(G, 1e-12)
@@ -123,7 +123,7 @@ class StaticGraphLinear(nn.Module):
 
     def forward(self, x: torch.Tensor, g: Optional[torch.Tensor] = None) -> torch.Tensor:
         g = self.ghat() if g is None else g
-        if (x.is_cuda and torch.is_grad_enabled() and x.dtype == torch.float32
+        if (x.is_cuda and _training.hip_gate() and x.dtype == torch.float32
                 and self.weight.dtype == torch.float32 and _training.hip_training_enabled()
                 and self._hip_ok(x, g)):
             # training on the device: forward + backward on the HIP kernels (sd_train.hip)
@@ -157,7 +157,7 @@ class RMSNorm(nn.Module):
         self.g = Parameter(torch.ones(1, 1, dim))
 
     def forward(self, x):
-        if (x.is_cuda and torch.is_grad_enabled() and x.dtype == torch.float32 and self.g.dtype == torch.float32
+        if (x.is_cuda and _training.hip_gate() and x.dtype == torch.float32 and self.g.dtype == torch.float32
                 and _training.hip_training_enabled() and x.shape[-1] <= 1024 and self.g.numel() == x.shape[-1]):
             # training on the device: forward + backward on HIP (sd_train.hip k_rmsnorm)
             return _training.rmsnorm(x, self.g, x.shape[-1] ** 0.5, 1e-12)
@@ -226,7 +226,7 @@ class ResnetBlock(nn.Module):
         scale_shift = None
         if self.mlp is not None and time_emb is not None:
             ss = self.mlp(time_emb).unsqueeze(1)
-            if (ss.is_cuda and torch.is_grad_enabled() and ss.dtype == torch.float32 and x.dim() == 3
+            if (ss.is_cuda and _training.hip_gate() and ss.dtype == torch.float32 and x.dim() == 3
                     and _training.hip_training_enabled() and isinstance(self.block1.norm, nn.Identity)
                     and x.shape[0] <= 65535):
                 # training on the device: block1's FiLM + tanh forward and backward on HIP
@@ -264,7 +264,7 @@ class Attention(nn.Module):
     def forward(self, x):
         b, n, _ = x.shape
         qkv = self.to_qkv(x)
-        if (qkv.is_cuda and torch.is_grad_enabled() and qkv.dtype == torch.float32 and _training.hip_training_enabled()
+        if (qkv.is_cuda and _training.hip_gate() and qkv.dtype == torch.float32 and _training.hip_training_enabled()
                 and isinstance(self.q_norm, nn.Identity) and isinstance(self.k_norm, nn.Identity)
                 and (not self.training or self.attn_dropout.p == 0.0) and 1 <= n <= 64 and 1 <= self.dim_head <= 64):
             # training on the device: the attention core forward + backward on HIP (sd_train.hip)

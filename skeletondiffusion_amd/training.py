@@ -16,11 +16,18 @@ tensor, grad is enabled and `hip_training_enabled()`; there is no silent CPU fal
 `graph_gru` / `gx_table` are the graph-GRU sequence core and its per-step mixing matrices for
 stage-1 training of the motion autoencoder (`sd_gru_train_*`, `sd_gx_table_*`,
 csrc/sd_gru_train.hip), under the same switch.
+
+`hip_forward_only()` lets the same forward kernels serve a forward under `no_grad`, and
+`q_sample_groups` is the forward process for k noisy copies per sequence (`sd_q_sample_groups`,
+csrc/sd_q_sample.hip): the two pieces of the selected-row best-of-k step (core/best_of_k.py,
+DESIGN.md §4w).
 """
 from __future__ import annotations
 
 import collections
+import contextlib
 import ctypes
+import threading
 from typing import Optional
 
 import torch
@@ -39,6 +46,32 @@ def set_hip_training(enabled: bool) -> bool:
 
 def hip_training_enabled() -> bool:
     return _ENABLED
+
+
+_FORWARD_ONLY = threading.local()
+
+
+@contextlib.contextmanager
+def hip_forward_only():
+    """While active (this thread only), the HIP training kernels also serve forwards that run with
+    grad disabled: every gate that reads `hip_gate()` passes under `torch.no_grad()`, the same
+    forward kernels run and autograd keeps nothing for a backward.  Off by default; with it off
+    every gate evaluates exactly as `torch.is_grad_enabled()`."""
+    prev = getattr(_FORWARD_ONLY, "on", False)
+    _FORWARD_ONLY.on = True
+    try:
+        yield
+    finally:
+        _FORWARD_ONLY.on = prev
+
+
+def hip_forward_only_active() -> bool:
+    return getattr(_FORWARD_ONLY, "on", False)
+
+
+def hip_gate() -> bool:
+    """The autograd condition of every HIP training gate: grad enabled, or `hip_forward_only()`."""
+    return torch.is_grad_enabled() or getattr(_FORWARD_ONLY, "on", False)
 
 
 MAX_NODES = 64  # sd_gl_train_forward / _backward: 1 <= J <= 64
@@ -544,6 +577,58 @@ def best_of_k(loss: torch.Tensor, k: int, sim: Optional[torch.Tensor] = None):
     if sim is not None and (sim.numel() != loss.numel() or sim.device != loss.device):
         raise ValueError("best_of_k: sim must hold one value per loss, on the same device")
     return BestOfKFunction.apply(loss, sim, int(k))
+
+
+def q_sample_groups(x0: torch.Tensor, t: torch.Tensor, sqrt_alphas_cumprod: torch.Tensor, k: int,
+                    M: Optional[torch.Tensor] = None, sqrt_one_minus_alphas_cumprod: Optional[torch.Tensor] = None,
+                    sel: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, seed: int = 0,
+                    step: int = 0, row0: int = 0, return_noise: bool = False):
+    """The forward process for k copies of each of the nseq sequences on HIP (`sd_q_sample_groups`),
+    no grad: x0 (nseq, J, D), t (nseq,) and either M (T, J, J) = Umm_sqrt_Lambda_bar_t or
+    sqrt_one_minus_alphas_cumprod (T,) -> x_t (nseq * k, J, D) in repeat_interleave order, or with
+    `sel` (nseq,) the copy sel[s] of each sequence, (nseq, J, D), bit for bit those rows of the full
+    launch.  The noise is `noise` (nseq * k, J, D) when given, else the device Philox stream keyed
+    (seed, step, row0 + row); `return_noise` also returns the noise of the rows written."""
+    if not x0.is_cuda or x0.dtype != torch.float32 or x0.dim() != 3:
+        raise ValueError("q_sample_groups: x0 must be a (nseq, J, D) fp32 device tensor")
+    nseq, J, D = x0.shape
+    dev = x0.device
+
+    def table(v, name, shape):
+        if v.dtype != torch.float32 or v.device != dev or v.dim() != 1 + len(shape) or tuple(v.shape[1:]) != shape:
+            raise ValueError(f"q_sample_groups: {name} must be a {('T',) + shape} fp32 tensor on x0's device")
+        return v.detach().contiguous()
+
+    ac = table(sqrt_alphas_cumprod, "sqrt_alphas_cumprod", ())
+    T = int(ac.shape[0])
+    Mc = None if M is None else table(M, "M", (J, J))
+    bc = None if sqrt_one_minus_alphas_cumprod is None else table(sqrt_one_minus_alphas_cumprod,
+                                                                  "sqrt_one_minus_alphas_cumprod", ())
+    for v, name in ((Mc, "M"), (bc, "sqrt_one_minus_alphas_cumprod")):
+        if v is not None and v.shape[0] != T:
+            raise ValueError(f"q_sample_groups: {name} must hold T = {T} timesteps")
+    if t.numel() != nseq:
+        raise ValueError(f"q_sample_groups: t must hold one timestep per sequence ({nseq})")
+    tc = t.detach().to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+    sc = None
+    if sel is not None:
+        if sel.numel() != nseq:
+            raise ValueError(f"q_sample_groups: sel must hold one index per sequence ({nseq})")
+        sc = sel.detach().to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+    nc = None
+    if noise is not None:
+        if tuple(noise.shape) != (nseq * k, J, D) or noise.dtype != torch.float32 or noise.device != dev:
+            raise ValueError(f"q_sample_groups: noise must be a ({nseq * k}, {J}, {D}) fp32 tensor on x0's device, "
+                             f"got {tuple(noise.shape)}")
+        nc = noise.detach().contiguous()
+    rows = nseq if sc is not None else nseq * k
+    xc = x0.detach().contiguous()
+    x_t = torch.empty(rows, J, D, device=dev, dtype=torch.float32)
+    eps = torch.empty_like(x_t) if return_noise else None
+    _lib.check(_lib.lib().sd_q_sample_groups(
+        xc.data_ptr(), tc.data_ptr(), ac.data_ptr(), _lib.ptr(Mc), _lib.ptr(bc), T, nseq, int(k), J, D, _lib.ptr(sc),
+        _lib.ptr(nc), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), int(row0), x_t.data_ptr(), _lib.ptr(eps), _stream(dev)))
+    return (x_t, eps) if return_noise else x_t
 
 
 def pose_loss(pred: torch.Tensor, target: torch.Tensor, mse: bool) -> torch.Tensor:
