@@ -68,8 +68,9 @@ SD_HD uint32_t xcd_remap(uint32_t block, uint32_t q8, uint32_t r8) {
 // (DESIGN.md §4v), so the blocks keep their smallest whole-line size
 constexpr int kGl4ArgsPadLines = 0;
 
-// GEMM phase: k_gl4t and k_gl4y.  Y element (row 32 tr + r, node j, column 32 t + c) goes to
-// y + tr y_ts + j y_js + t y_cs + r y_rs + c.  The first three lines hold what a workgroup needs
+// GEMM phase: k_gl4t and k_gl4y.  The Y tile (row tile tr, node j, column tile t) starts at
+// y + tr y_ts + j y_js + t y_cs; inside it, the scratch's block layout or rows y_rs apart
+// (sd_ystore_map.h).  The first three lines hold what a workgroup needs
 // before its first operand load (gl4g_preload: one batch of scalar loads, one wait); the last line
 // what only the stores and the exact-f32 fallback read.
 struct GL4GArgs {

@@ -31,6 +31,7 @@
 
 #include "sd_gl4_args.h"
 #include "sd_internal.h"
+#include "sd_ystore_map.h"
 
 namespace sd {
 
@@ -44,6 +45,8 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 namespace {
 
 typedef __attribute__((address_space(3))) void lds_void;
+typedef __attribute__((address_space(3))) float lds_float;
+typedef __attribute__((address_space(3))) floatx4 lds_floatx4;
 
 template <int N>
 struct VmCnt4 {
@@ -197,12 +200,12 @@ hipError_t make_split_weights(const float* W, int ntypes, int N, int K, SplitW* 
 // chunk), RMS sum, range guard and scale arithmetic as in k_gl4, so phase 2 (k_gl4 MODE 2 / 3)
 // reproduces the one-kernel results bit for bit.  Workgroup = 4 waves = 4 column tiles of one
 // (row tile, node): the x fragments are shared through L1.
-// Output: element (row 32 tr + r, node j, column 32 t + c) at y + tr y_ts + j y_js + t y_cs +
-// r y_rs + c.  The split route's scratch p.zs is column-tiled, [tile][32-column tile][node][32
-// rows][32] (y_cs = J * 1024: every (tile, column tile, node) block is 4 contiguous KiB, written
-// whole by one wave and read back in 1-2 KiB runs by the mixing phase -- round 4; it was
-// [tile][node][32 rows][N], 128-B runs); (ROWMAJOR, v5 for J > 21) row-major z with y_cs = 32,
-// rows < B only.
+// Output: the 32 x 32 tile (row tile tr, node j, column tile t) starts at y + tr y_ts + j y_js +
+// t y_cs.  The split route's scratch p.zs is column-tiled, [tile][32-column tile][node] blocks of 4
+// contiguous KiB (y_cs = J * 1024), written whole by one wave and read back in 256-B / 512-B runs
+// by the mixing phase; inside a block [8-column group][32 rows][8], the order the swapped-operand
+// accumulators store in (sd_ystore_map.h).  (ROWMAJOR, v5 for J > 21) row-major z:
+// element (r, c) of the tile at r y_rs + c, y_cs = 32, rows < B only.
 struct YDst {  // host side: where a GEMM phase writes (packed into GL4GArgs by the launchers)
     float* y;
     int64_t y_rs, y_js, y_ts, y_cs;
@@ -216,10 +219,7 @@ struct YOut {
     GL4GArgs g;
 };
 static_assert(sizeof(YOut) == sizeof(GL4GArgs), "YOut: the GEMM-phase block");
-// zs element (row, node j, column n) of the split route's column-tiled scratch
-__device__ __forceinline__ int64_t zs_off(int64_t row, int j, int n, int J, int N) {
-    return ((((row >> 5) * (N >> 5) + (n >> 5)) * J + j) << 10) + ((row & 31) << 5) + (n & 31);
-}
+// (zs_off, the scratch's element map, and the GEMM phase's store map: sd_ystore_map.h)
 
 // f16 range fallback (round 5; was a host-side re-run of the whole call): a wave whose split-f16
 // operands reached |x| >= 65504 (x_hi would be inf) recomputes its 32 x 32 tile -- rows row0 ..
@@ -235,6 +235,10 @@ __device__ __forceinline__ int64_t zs_off(int64_t row, int j, int n, int J, int 
 // spilled 4-8x more), as a call with acc live too (the live values move to callee-saved
 // registers).  So the callers run it AFTER their normal stores, in a rolled loop over the tiles,
 // inlined (no call frame, no scratch), and store the exact tile over the first.
+// SWAP: the operands exchanged (weights as A, x as B), so the tile comes back transposed, in the
+// GEMM phases' store layout (sd_ystore_map.h: lane = row l32, register 4 g + e = column 8 g + 4 h + e);
+// per element the same products in the same k order, so the same bits.
+template <bool SWAP = false>
 __device__ __forceinline__ floatx16 exact_tile_f32_impl(const float* x1, int64_t x1_rs, int K1, int x1_div,
                                                                   int64_t x1_row0, int x1_blk, const float* x2,
                                                                   int64_t x2_rs, int K2, int x2_blk, int64_t B, int J,
@@ -258,10 +262,17 @@ __device__ __forceinline__ floatx16 exact_tile_f32_impl(const float* x1, int64_t
         const float4 xv = *reinterpret_cast<const float4*>(xp);
         float4 wv = *reinterpret_cast<const float4*>(wr + k0);
         if (col >= N) wv = float4{0.f, 0.f, 0.f, 0.f};
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(xv.x, wv.x, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(xv.y, wv.y, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(xv.z, wv.z, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(xv.w, wv.w, c, 0, 0, 0);
+        if constexpr (SWAP) {
+            c = __builtin_amdgcn_mfma_f32_32x32x2f32(wv.x, xv.x, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x2f32(wv.y, xv.y, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x2f32(wv.z, xv.z, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x2f32(wv.w, xv.w, c, 0, 0, 0);
+        } else {
+            c = __builtin_amdgcn_mfma_f32_32x32x2f32(xv.x, wv.x, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x2f32(xv.y, wv.y, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x2f32(xv.z, wv.z, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x2f32(xv.w, wv.w, c, 0, 0, 0);
+        }
     }
     const float up = 1.0f / unscale;
 #pragma unroll
@@ -341,11 +352,11 @@ __global__ __launch_bounds__(256) void k_gl4y(const GL4GArgs p) {
         const floatx8 a = __builtin_elementwise_abs(f);
         amx = fmaxf(amx, fmaxf(fmaxf(fmaxf(a[0], a[1]), fmaxf(a[2], a[3])), fmaxf(fmaxf(a[4], a[5]), fmaxf(a[6], a[7]))));
         const halfx8 xh = __builtin_convertvector(f, halfx8);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh, wh[sl], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[sl], xh, acc, 0, 0, 0);
         if constexpr (!PREC) {
             const halfx8 xl = __builtin_convertvector(f - __builtin_convertvector(xh, floatx8), halfx8);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh, wl[sl], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(xl, wh[sl], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[sl], xh, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[sl], xl, acc, 0, 0, 0);
         }
     };
     // nchunk % PF == 0 (launch_gl4y): every load issued unconditionally -- a main loop that always
@@ -365,46 +376,54 @@ __global__ __launch_bounds__(256) void k_gl4y(const GL4GArgs p) {
             issue(c0 + i + PF, i);
         }
     }
+    // the bias to this wave's 32 floats of LDS, before the last round (every load is issued; the bias
+    // is the oldest): with the weights as the A operand a lane holds one batch row and 16 columns of
+    // the tile (sd_ystore_map.h), and reads its columns' bias back as 16-B pieces in the epilogue
+    __shared__ __attribute__((aligned(16))) float sBy[4 * 32];
+    float* sB = sBy + wave * 32;
+    sB[l32] = bv;
 #pragma unroll
     for (int i = 0; i < PF; ++i) compute(nchunk - PF + i, i);
     // the range guard sees the real rows only (the padding rows of a row-blocked buffer hold
     // whatever the workspace held: never stored, but they must not trigger the fallback)
     const bool oor = __builtin_amdgcn_ballot_w64(arow < p.B && amx >= 65504.0f) != 0;  // wave-uniform
-    float sc[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) sc[r] = p.wsp_unscale;
+    float sc = p.wsp_unscale;  // one scale per lane: its own row's
     if (RMS) {
         const float t = ss + __shfl_xor(ss, 32);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float n2 = __shfl(t, (r & 3) + 8 * (r >> 2) + 4 * h);
-            sc[r] *= 1.0f / fmaxf(sqrtf(n2), 1e-12f);
-        }
+        sc *= 1.0f / fmaxf(sqrtf(t), 1e-12f);
     }
+    // 4 dwordx4 stores per tile (registers 4 g .. 4 g + 3 = columns 8 g + 4 h .. + 3 of row l32);
+    // scalar stores only where a row-major destination cannot take 16-B pieces (wave-uniform)
+    const bool vec = !ROWMAJOR || ((((uintptr_t)p.y) & 15) == 0 && (p.y_rs & 3) == 0 && (p.N & 3) == 0);
     auto store = [&](const floatx16& v) {
-        if constexpr (ROWMAJOR) {
-            if (ncol < p.N) {
-                float* y = p.y + tr * p.y_ts + (int64_t)j * p.y_js + (int64_t)tc * p.y_cs + l32;
+        if (ROWMAJOR && arow >= p.B) return;  // row-major z holds rows < B only
+        float* y = p.y + tr * p.y_ts + (int64_t)j * p.y_js + (int64_t)tc * p.y_cs +
+                   (ROWMAJOR ? ystore_rm_piece_off(l32, h, 0, p.y_rs) : ystore_zs_piece_off(l32, h, 0));
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int rr = (r & 3) + 8 * (r >> 2) + 4 * h;
-                    if (row0 + rr < p.B) y[(int64_t)rr * p.y_rs] = v[r] * sc[r] + bv;
-                }
+        for (int g = 0; g < 4; ++g) {
+            const floatx4 b4 = *reinterpret_cast<const floatx4*>(sB + ystore_col(g, h));
+            floatx4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = v[4 * g + e] * sc + b4[e];
+            const int col = tc * 32 + ystore_col(g, h);
+            if (vec) {  // N % 4 == 0: a piece is inside or outside as a whole (the scratch: N % 32 == 0)
+                if (!ROWMAJOR) *reinterpret_cast<floatx4*>(y + ystore_zs_piece_off(0, 0, g)) = o;
+                else if (col < p.N) *reinterpret_cast<floatx4*>(y + ystore_col(g, 0)) = o;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (col + e < p.N) y[ystore_col(g, 0) + e] = o[e];
             }
-        } else {  // the split route's column-tiled scratch (zs_off through the strides: y_rs = 32): every
-                  // row of the tile, N % 32 == 0
-            float* y = p.y + tr * p.y_ts + (int64_t)j * p.y_js + (int64_t)tc * p.y_cs + l32;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) y[((r & 3) + 8 * (r >> 2) + 4 * h) << 5] = v[r] * sc[r] + bv;
         }
     };
     store(acc);
-    // f16 range left: the tile again on exact-f32 MFMA, stored over the first (same lanes, same
-    // addresses: program order); after the stores, so no accumulator is live across the call
+    // f16 range left: the tile again on exact-f32 MFMA (operands swapped: the same lane layout), stored
+    // over the first (same lanes, same addresses: program order); after the stores, so no accumulator
+    // is live across the call
     if (oor) {
         if (p.status && lane == 0) atomicOr(p.status, 1u);
-        store(exact_tile_f32_impl(p.x1, p.x1_rs, p.K1, p.x1_div, p.x1_row0, p.x1_blk, p.x2, p.x2_rs, p.K2, p.x2_blk, p.B, p.J,
-                                  p.W, jt * p.N, p.N, p.wsp_unscale, row0, j, tc * 32));
+        store(exact_tile_f32_impl<true>(p.x1, p.x1_rs, p.K1, p.x1_div, p.x1_row0, p.x1_blk, p.x2, p.x2_rs, p.K2, p.x2_blk, p.B,
+                                        p.J, p.W, jt * p.N, p.N, p.wsp_unscale, row0, j, tc * 32));
     }
 }
 
@@ -433,11 +452,17 @@ __global__ __launch_bounds__(256) void k_gl4y(const GL4GArgs p) {
 // N = 192, 3,200 rows 17.1 vs 20.7 us (RT 2, CT 3), 1,067 rows 10.8 vs 12.5; N = 768 (RT 1, CT 6)
 // 53.6 vs 56.6 and 23.3 vs 25.9 (profiles/r06f/probe.txt).  bf16 operands (PREC 2) are their own A
 // fragments and keep the tracked register ring of the round-5 form (RT = 1).
-template <int PREC, int CT, int NCH, int PF>
+// bytes of the weight ring; ROWMAJOR: at least the four waves' 32 x 32 output transposes (TS = 36
+// floats per row), which take the ring's place after the K loop
+template <int PREC, int CT, int PF, bool ROWMAJOR>
+constexpr int gl4t_ring_bytes() {
+    constexpr int TILE_H = PREC ? 512 : 1024, NWV = 4, NS = PF + 1, TR = NWV * 32 * 36 * 4;
+    return !ROWMAJOR || NS * CT * TILE_H * 2 > TR ? NS * CT * TILE_H * 2 : TR;
+}
+template <int PREC, int CT, int NCH, int PF, bool ROWMAJOR>
 constexpr int gl4t_smem_bytes() {
-    constexpr int TILE_H = PREC ? 512 : 1024, TS = 36, NWV = 4, NS = PF + 1;
-    constexpr int SBW = NS * CT * TILE_H * 2;
-    return SBW > NWV * 32 * TS * 4 ? SBW : NWV * 32 * TS * 4;
+    // the weight ring + each wave's copy of the workgroup's CT x 32 bias floats
+    return gl4t_ring_bytes<PREC, CT, PF, ROWMAJOR>() + 4 * CT * 32 * 4;
 }
 
 // A 16-B global load the compiler does not track (k_gl4t's x ring): waited for by hand (counted
@@ -456,10 +481,18 @@ __device__ __forceinline__ void gl4t_body(const GL4GArgs& p, const Unit3 un, con
     constexpr int NT = NWV * 64;
     constexpr int TILE_H = PREC ? 512 : 1024;   // halves of one 32-column tile per chunk
     constexpr int PPT = TILE_H / 8;             // 16-B pieces per tile
-    constexpr int TS = 36;                      // floats per row of a wave's 32 x 32 output transpose
     constexpr int NS = PF + 1;                  // ring slots: chunk c in slot c % NS
     constexpr bool XV = PREC != 2;              // x by untracked register loads
     _Float16(*sW)[CT * TILE_H] = reinterpret_cast<_Float16(*)[CT * TILE_H]>(smem_raw);
+    // behind the ring: this wave's own copy of the workgroup's CT x 32 bias floats (written and read
+    // by the same wave: DS operations of one wave complete in order, no barrier)
+    // The lane's write slot (column l32 of tile 0) and its first 16-B read piece (columns 4 h .. + 3),
+    // worked out and pinned here: the other tiles and pieces are immediate offsets, so no address
+    // arithmetic is left for the scheduler to put between a ring wait and its s_barrier.
+    float* sB = reinterpret_cast<float*>(smem_raw + gl4t_ring_bytes<PREC, CT, PF, ROWMAJOR>()) + (tid >> 6) * (CT * 32);
+    lds_float* sBw = (lds_float*)(sB + (tid & 31));
+    const lds_floatx4* sBr = (const lds_floatx4*)(sB + 4 * ((tid >> 5) & 1));
+    asm volatile("" : "+v"(sBw), "+v"(sBr));
     const int lane = tid & 63, l32 = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int J = p.J;
@@ -517,10 +550,19 @@ __device__ __forceinline__ void gl4t_body(const GL4GArgs& p, const Unit3 un, con
     for (int rt = 0; rt < RT; ++rt) ss[rt] = amx[rt] = 0.f;
     // the epilogue's bias, loaded before the K loop: loaded per tile in the epilogue, each load was
     // the youngest memory op and its vmcnt(0) also waited for the previous tile's stores -- CT
-    // serial memory round trips in the store tail
+    // serial memory round trips in the store tail.  A lane of the transposed accumulators holds 16
+    // columns per tile, so the values go through LDS (sB): lane l32 loads column l32 of every tile here,
+    // by a load the compiler does not track (as the x ring's: a tracked one would get its own vmcnt
+    // wait, counted without the ring's loads, at the LDS write); the loads are older than every fill,
+    // so chunk 0's counted wait covers them, and the LDS write follows that wait (below)
     float bvp[CT];
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct) bvp[ct] = p.bias ? p.bias[jt * p.N + (cg * CT + ct) * 32 + l32] : 0.f;
+    for (int ct = 0; ct < CT; ++ct) {
+        // (no bias: any readable word -- the weights -- loaded and dropped, so that no branch and no
+        // copy of a register still being written sits between the load and its fence)
+        const float* bsrc = p.bias ? p.bias + jt * p.N + (cg * CT + ct) * 32 + l32 : reinterpret_cast<const float*>(p.wsp);
+        asm volatile("global_load_dword %0, %1, off" : "=v"(bvp[ct]) : "v"(bsrc) : "memory");
+    }
     const _Float16* wt0 = p.wsp + ((int64_t)jt * NCH * p.wsp_nct + cg * CT) * 1024;
     // Pieces of wave w per chunk: q0 = 64 w + NT k < CT * PPT (two counts, wave-uniform).
     constexpr int NPC = CT * PPT;
@@ -580,7 +622,7 @@ __device__ __forceinline__ void gl4t_body(const GL4GArgs& p, const Unit3 un, con
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
                 const bf16x8 wb = *reinterpret_cast<const bf16x8*>(wt + ct * TILE_H);
-                acc[0][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xb16, wb, acc[0][ct], 0, 0, 0);
+                acc[0][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wb, xb16, acc[0][ct], 0, 0, 0);
             }
             return;
         }
@@ -611,10 +653,10 @@ __device__ __forceinline__ void gl4t_body(const GL4GArgs& p, const Unit3 un, con
             if constexpr (!PREC) wl = *reinterpret_cast<const halfx8*>(wt + ct * TILE_H + 512);
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
-                floatx16 t = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh[rt], wh, acc[rt][ct], 0, 0, 0);
+                floatx16 t = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh[rt], acc[rt][ct], 0, 0, 0);
                 if constexpr (!PREC) {
-                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh[rt], wl, t, 0, 0, 0);
-                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(xl[rt], wh, t, 0, 0, 0);
+                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh[rt], t, 0, 0, 0);
+                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl[rt], t, 0, 0, 0);
                 }
                 acc[rt][ct] = t;
             }
@@ -657,6 +699,13 @@ __device__ __forceinline__ void gl4t_body(const GL4GArgs& p, const Unit3 un, con
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
         wait_chunk(c, NCH - 1 - c < PF - 1 ? NCH - 1 - c : PF - 1);
+        if (c == 0) {  // the bias loads are older than chunk 0's: landed; fenced, then to this wave's LDS copy
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) {
+                asm volatile("" : "+v"(bvp[ct]));
+                sBw[ct * 32] = p.bias ? bvp[ct] : 0.f;
+            }
+        }
         if constexpr (XV) {  // fill first: the slots of chunk c - 1 are free after the barrier
             if (c + PF < NCH) fill(c + PF);
             asm volatile("" ::: "memory");
@@ -668,57 +717,69 @@ __device__ __forceinline__ void gl4t_body(const GL4GArgs& p, const Unit3 un, con
         }
         asm volatile("" ::: "memory");
     }
-    __syncthreads();  // every wave past its last chunk: the stages become the output transposes
-    // Y = acc * sc + bias through a per-wave 32 x 32 LDS transpose (the stages are dead: every
-    // wave is past its last chunk), stored as 16-B pieces: 4 dwordx4 instead of 16 dword stores
-    // per tile.  Launch shapes: N a multiple of 32 CT (launch_gl4t), so every column is real.
+    // Y = acc * sc + bias straight from the accumulators (sd_ystore_map.h): with the weights as the A
+    // operand a lane holds ONE batch row (l32) and, in registers 4 g .. 4 g + 3, the four consecutive
+    // columns 8 g + 4 h .. + 3 of the tile -- a 16-B piece: 4 dwordx4 stores per tile, no LDS transpose
+    // and no barrier (the ring is not reused: a wave stores as soon as its own last MFMAs are done).
+    // One scale per lane (its row's).  Launch shapes: N a multiple of 32 CT (launch_gl4t), so every
+    // column is real.
+    // ROWMAJOR (z of the J > 21 path: rows J N floats apart) keeps a per-wave LDS transpose: stored
+    // directly, an instruction would write 32 B to each of 32 rows (MANO J = 51 measured 2.8 % slower);
+    // through the transpose it writes 128 B to each of 8.  The transposes take the ring's place, so
+    // every wave must be past its last chunk; the pieces go in as 4 ds_write_b128.
+    constexpr int TS = 36;  // floats per row of a transpose
     float* sT = reinterpret_cast<float*>(smem_raw) + wave * 32 * TS;
+    if constexpr (ROWMAJOR) __syncthreads();
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
         const int64_t tr = tr0 + rt;
         if (tr >= ntile_r) break;  // wave-uniform: dead tiles store nothing
         // (real rows only: the padding rows of a row-blocked buffer are never stored)
         const bool oor = PREC != 2 && __builtin_amdgcn_ballot_w64(arow[rt] < p.B && amx[rt] >= 65504.0f) != 0;
-        float sc[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sc[r] = unscale;
+        float sc = unscale;
         if (RMS) {
-            const float t = ss[rt] + __shfl_xor(ss[rt], 32);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float n2 = __shfl(t, (r & 3) + 8 * (r >> 2) + 4 * h);
-                sc[r] *= 1.0f / fmaxf(sqrtf(n2), 1e-12f);
-            }
+            const float t = ss[rt] + __shfl_xor(ss[rt], 32);  // the lane's own row
+            sc *= 1.0f / fmaxf(sqrtf(t), 1e-12f);
         }
-        float* y = p.y + tr * p.y_ts + (int64_t)j * p.y_js + (int64_t)cg * CT * p.y_cs;  // as k_gl4y's
-        auto store_tile = [&](int ct, const floatx16& v, float bv) {
+        float* y = p.y + tr * p.y_ts + (int64_t)j * p.y_js + (int64_t)cg * CT * p.y_cs + (ROWMAJOR ? 0 : ystore_zs_piece_off(l32, h, 0));
+        auto store_tile = [&](int ct, const floatx16& v) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) sT[((r & 3) + 8 * (r >> 2) + 4 * h) * TS + l32] = v[r] * sc[r] + bv;
-            __builtin_amdgcn_wave_barrier();  // DS operations of one wave complete in order
+            for (int g = 0; g < 4; ++g) {
+                const floatx4 bv = sBr[(ct * 32 + ystore_col(g, 0)) / 4];
+                floatx4 o;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int row = 8 * q + (lane >> 3), c4 = (lane & 7) * 4;
-                const floatx4 o = *reinterpret_cast<const floatx4*>(sT + row * TS + c4);
-                if (!ROWMAJOR || row0[rt] + row < p.B)  // row-major z holds rows < B only
-                    *reinterpret_cast<floatx4*>(y + (int64_t)row * p.y_rs + (int64_t)ct * p.y_cs + c4) = o;
+                for (int e = 0; e < 4; ++e) o[e] = v[4 * g + e] * sc + bv[e];
+                if constexpr (ROWMAJOR) *reinterpret_cast<floatx4*>(sT + l32 * TS + ystore_col(g, h)) = o;
+                else *reinterpret_cast<floatx4*>(y + (int64_t)ct * p.y_cs + ystore_zs_piece_off(0, 0, g)) = o;
             }
-            __builtin_amdgcn_wave_barrier();
+            if constexpr (ROWMAJOR) {
+                __builtin_amdgcn_wave_barrier();  // DS operations of one wave complete in order
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int row = 8 * q + (lane >> 3), c4 = (lane & 7) * 4;
+                    const floatx4 o = *reinterpret_cast<const floatx4*>(sT + row * TS + c4);
+                    if (row0[rt] + row < p.B)  // row-major z holds rows < B only
+                        *reinterpret_cast<floatx4*>(y + (int64_t)row * p.y_rs + (int64_t)ct * p.y_cs + c4) = o;
+                }
+                __builtin_amdgcn_wave_barrier();
+            }
         };
 #pragma unroll
-        for (int ct = 0; ct < CT; ++ct) store_tile(ct, acc[rt][ct], bvp[ct]);
-        // f16 range left: every tile of the row tile again on exact-f32 MFMA, stored over the first
-        // (same lanes, same addresses: program order) -- after the stores
+        for (int ct = 0; ct < CT; ++ct) store_tile(ct, acc[rt][ct]);
+        // f16 range left: every tile of the row tile again on exact-f32 MFMA (operands swapped: the
+        // same lane layout), stored over the first (same lanes, same addresses: program order) --
+        // after the stores
         if (oor) {
             if (p.status && lane == 0) atomicOr(p.status, 1u);
 #pragma nounroll
             for (int ct = 0; ct < CT; ++ct) {
                 const int col = (cg * CT + ct) * 32;
                 // (a paired launch: the tile's own layer -- its f32 weights, pair_n columns, its scale)
-                const floatx16 ex = exact_tile_f32_impl(p.x1, p.x1_rs, p.K1, p.x1_div, p.x1_row0, p.x1_blk, p.x2, p.x2_rs, p.K2,
-                                                        p.x2_blk, p.B, p.J, second ? p.W2 : p.W,
-                                                        jt * (p.pair_n ? p.pair_n : p.N), p.pair_n ? p.pair_n : p.N,
-                                                        unscale, row0[rt], j, second ? col - p.pair_n : col);
-                store_tile(ct, ex, p.bias ? p.bias[jt * p.N + col + l32] : 0.f);
+                const floatx16 ex = exact_tile_f32_impl<true>(p.x1, p.x1_rs, p.K1, p.x1_div, p.x1_row0, p.x1_blk, p.x2, p.x2_rs,
+                                                              p.K2, p.x2_blk, p.B, p.J, second ? p.W2 : p.W,
+                                                              jt * (p.pair_n ? p.pair_n : p.N), p.pair_n ? p.pair_n : p.N,
+                                                              unscale, row0[rt], j, second ? col - p.pair_n : col);
+                store_tile(ct, ex);
             }
         }
     }
@@ -726,7 +787,7 @@ __device__ __forceinline__ void gl4t_body(const GL4GArgs& p, const Unit3 un, con
 
 template <bool RMS, int PREC, int CT, int NCH, bool ROWMAJOR, int RT, int PF>
 __global__ __launch_bounds__(256, 2) void k_gl4t(const GLArgs, int, int64_t, const YOut yo) {
-    __shared__ __attribute__((aligned(16))) char smem_raw[gl4t_smem_bytes<PREC, CT, NCH, PF>()];
+    __shared__ __attribute__((aligned(16))) char smem_raw[gl4t_smem_bytes<PREC, CT, NCH, PF, ROWMAJOR>()];
     // XCD-aware order (k_gl4's): consecutive u -- the column groups of one (row group, node), which
     // read the same x -- on one XCD (blocks b, b + 8, ... share one), so x reaches that L2 once
     const GL4GArgs& p = yo.g;
@@ -1103,18 +1164,23 @@ __device__ __forceinline__ void gl4_body(const A& p, const int bx, const int nwg
         constexpr int NYL = (YQ + NTH - 1) / NTH, NGL = (J * J + NTH - 1) / NTH;
         constexpr int YS8 = 8 * COLS + 16;  // MODE 3: attention_epilogue's slab layout
         const int64_t tb = (row0 >> 5) * J;
-        // column-tiled zs (zs_off): consecutive q read consecutive 16-B pieces -- one node's rows of
-        // the slab in one column tile are a contiguous 1-2 KiB run
+        // column-tiled zs (zs_off, sd_ystore_map.h): consecutive q read consecutive 16-B pieces -- one
+        // node's rows of the slab in one column tile are four contiguous runs (one per 8 columns)
         (void)tb;
         auto ysrc = [&](int q, float*& dst) -> const float* {
             if constexpr (MODE == 2) {
                 static_assert(MODE != 2 || COLS == 32, "MODE 2: one 32-column tile");
-                const int cc = (q % C4) * 4, r = (q / C4) & 15, j = q / (16 * C4);
+                // (zs_slab_piece: consecutive q are consecutive in memory -- four 512-B runs per node)
+                const int j = q / (16 * C4);
+                int cc, r;
+                zs_slab_piece(q % (16 * C4), 16, &r, &cc);
                 dst = sY + j * YS + r * YR + cc;
                 // (a paired launch: this layer's columns of the wider scratch, GLArgs::zs_n / zs_c0)
                 return p.zs + zs_off(row0 + 16 * slab + r, j, p.zs_c0 + c0 + cc, J, p.zs_n);
             } else {
-                const int cc = (q & 7) * 4, rr = (q >> 3) & 7, j = (q >> 6) % J, ct = (q >> 6) / J;
+                const int j = (q >> 6) % J, ct = (q >> 6) / J;  // four 256-B runs per (column tile, node)
+                int cc, rr;
+                zs_slab_piece(q & 63, 8, &rr, &cc);
                 dst = sY + j * YS8 + rr * COLS + 32 * ct + cc;
                 return p.zs + zs_off(row0 + 8 * slab + rr, j, (ctile + ct * p.attn_heads) * 32 + cc, J, p.N);
             }
@@ -1784,7 +1850,8 @@ template <int J>
 static hipError_t gl4_split(const GLArgs& a, bool rms, bool attn, int route, hipStream_t s) {
     const int64_t ntile_r = (a.B + 31) / 32;
     const int ntc = a.N / 32;
-    const YDst yo{a.zs, 32, 1024, (int64_t)(a.N / 32) * J * 1024, (int64_t)J * 1024};  // column-tiled (zs_off)
+    const ZsStrides zst = zs_strides(J, a.N);  // column-tiled (zs_off)
+    const YDst yo{a.zs, 0, zst.y_js, zst.y_ts, zst.y_cs};  // (no row stride: a block is laid out by ystore_zs_piece_off)
     hipError_t e = route == 2 ? launch_gl4t<false>(a, rms, ntile_r, yo, s) : hipErrorNotSupported;
     if (e == hipErrorNotSupported) {
         if (a.prec == 2) return hipErrorNotSupported;  // k_gl4y has no bf16 form
@@ -1818,7 +1885,8 @@ static hipError_t gl4_split_dispatch(const GLArgs& a, bool rms, bool attn, int r
 template <int J>
 static hipError_t gl4_pair(const GLArgs& pr, const GLArgs& a, const GLArgs& b, hipStream_t s) {
     const int64_t ntile_r = (pr.B + 31) / 32;
-    const YDst yo{pr.zs, 32, 1024, (int64_t)(pr.N / 32) * J * 1024, (int64_t)J * 1024};  // as gl4_split, 2 N wide
+    const ZsStrides zst = zs_strides(J, pr.N);  // as gl4_split, 2 N wide
+    const YDst yo{pr.zs, 0, zst.y_js, zst.y_ts, zst.y_cs};
     const hipError_t e = launch_gl4t<false>(pr, false, ntile_r, yo, s);
     if (e != hipSuccess) return e;
     if (!gl4_grid_ok((int64_t)(a.N + b.N) / 32 * ntile_r * 2)) return hipErrorInvalidValue;
