@@ -473,12 +473,6 @@ int gru_check(const char* fn, int64_t rows, int T, int Ta, int Tg, int J, int H,
 }  // namespace
 }  // namespace sd
 
-#define GT_HIP(x)                                                                                     \
-    do {                                                                                              \
-        hipError_t e_ = (x);                                                                          \
-        if (e_ != hipSuccess) return sd::set_error(SD_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 extern "C" {
 
 size_t sd_gru_train_workspace_bytes(int64_t rows, int32_t T, int32_t J, int32_t H, int32_t n_types) {
@@ -512,11 +506,11 @@ int sd_gru_train_forward(const float* a, int32_t Ta, const float* h0, const floa
     const int64_t nw = (int64_t)types * H3 * H;
     hipLaunchKernelGGL(sd::k_gru_transpose_w, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, W_hh, (int64_t)types, H,
                        w.wt);
-    GT_HIP(hipGetLastError());
+    SD_HIP(hipGetLastError());
     if (keep) {
         hipLaunchKernelGGL(sd::k_gru_copy_rows, dim3((unsigned)((rows * JH + 255) / 256)), dim3(256), 0, s, h0, JH, hprev,
                            (int64_t)T * JH, rows, (int)JH);
-        GT_HIP(hipGetLastError());
+        SD_HIP(hipGetLastError());
     }
     const int hh_threads = ((H3 < 1024 ? H3 : 1024) + 63) & ~63;
     const dim3 hh_grid((unsigned)J, (unsigned)((rows + sd::kGruRT - 1) / sd::kGruRT));
@@ -527,13 +521,13 @@ int sd_gru_train_forward(const float* a, int32_t Ta, const float* h0, const floa
         float* ct = keep ? c + (int64_t)t * JH3 : w.ctmp;
         const int64_t c_rs = keep ? (int64_t)T * JH3 : JH3;
         hipLaunchKernelGGL(sd::k_gru_hh, hh_grid, dim3(hh_threads), 0, s, hp, hp_rs, w.wt, b_hh, nt, ct, c_rs, rows, J, H);
-        GT_HIP(hipGetLastError());
+        SD_HIP(hipGetLastError());
         const float* at = a + (int64_t)sd::gru::step_of(t, Ta) * JH3;
         float* hn = (keep && t + 1 < T) ? hprev + (int64_t)(t + 1) * JH : nullptr;
         hipLaunchKernelGGL(sd::k_gru_gate, gate_grid, dim3(256), 0, s, at, (int64_t)Ta * JH3, ct, c_rs,
                            gx + sd::gru::step_of(t, Tg) * J * J, hp, hp_rs, hs + (int64_t)t * JH, (int64_t)T * JH, hn,
                            (int64_t)T * JH, keep ? gates + (int64_t)t * J * 4 * H : nullptr, (int64_t)T * J * 4 * H, J, H);
-        GT_HIP(hipGetLastError());
+        SD_HIP(hipGetLastError());
     }
     return SD_OK;
 }
@@ -548,9 +542,9 @@ int sd_gru_train_backward(const float* dhs, const float* a, int32_t Ta, const fl
     const int types = n_types > 0 ? n_types : 1;
     const int H3 = 3 * H;
     if (rows == 0) {  // empty batch: zero parameter gradients
-        if (dgx) GT_HIP(hipMemsetAsync(dgx, 0, (size_t)Tg * J * J * sizeof(float), s));
-        if (dW_hh) GT_HIP(hipMemsetAsync(dW_hh, 0, (size_t)types * H3 * H * sizeof(float), s));
-        if (db_hh) GT_HIP(hipMemsetAsync(db_hh, 0, (size_t)types * H3 * sizeof(float), s));
+        if (dgx) SD_HIP(hipMemsetAsync(dgx, 0, (size_t)Tg * J * J * sizeof(float), s));
+        if (dW_hh) SD_HIP(hipMemsetAsync(dW_hh, 0, (size_t)types * H3 * H * sizeof(float), s));
+        if (db_hh) SD_HIP(hipMemsetAsync(db_hh, 0, (size_t)types * H3 * sizeof(float), s));
         return SD_OK;
     }
     if (!dhs) return sd::set_error(SD_E_INVALID, "sd_gru_train_backward: dhs is null");
@@ -570,17 +564,17 @@ int sd_gru_train_backward(const float* dhs, const float* a, int32_t Ta, const fl
     for (int t = T - 1; t >= 0; --t) {
         hipLaunchKernelGGL(sd::k_gru_gate_bwd, dim3(ew_blocks), dim3(256), 0, s, dhs, t == T - 1 ? nullptr : w.dhc, gates,
                            hprev, w.dP, w.dhz, rows, T, t, J, H);
-        GT_HIP(hipGetLastError());
+        SD_HIP(hipGetLastError());
         hipLaunchKernelGGL(sd::k_gru_bwd_hh, hh_grid, dim3(256), 0, s, w.dP, gx + sd::gru::step_of(t, Tg) * J * J, W_hh,
                            nt, w.dhz, w.dc, w.dhc, rows, T, t, J, H);
-        GT_HIP(hipGetLastError());
+        SD_HIP(hipGetLastError());
     }
-    if (dh0) GT_HIP(hipMemcpyAsync(dh0, w.dhc, (size_t)rows * JH * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (dh0) SD_HIP(hipMemcpyAsync(dh0, w.dhc, (size_t)rows * JH * sizeof(float), hipMemcpyDeviceToDevice, s));
     // batched over all rows x steps
     if (da) {
         hipLaunchKernelGGL(sd::k_gru_da, dim3((unsigned)(rows * Ta), (unsigned)((H3 + 63) / 64)), dim3(256), 0, s, w.dP,
                            gx, Tg, da, Ta, T, J, H);
-        GT_HIP(hipGetLastError());
+        SD_HIP(hipGetLastError());
     }
     if (dgx) {
         const int chunks = (int)((rows + sd::kGruDgxRows - 1) / sd::kGruDgxRows);
@@ -591,21 +585,21 @@ int sd_gru_train_backward(const float* dhs, const float* a, int32_t Ta, const fl
             hipLaunchKernelGGL(sd::k_gru_dgx_part<2>, grid, dim3(256), 0, s, w.dP, a, Ta, c, w.part, rows, T, J, H);
         else
             hipLaunchKernelGGL(sd::k_gru_dgx_part<4>, grid, dim3(256), 0, s, w.dP, a, Ta, c, w.part, rows, T, J, H);
-        GT_HIP(hipGetLastError());
+        SD_HIP(hipGetLastError());
         const int cnt = (Tg == 1 ? T : 1) * chunks;
         const int64_t total = (int64_t)Tg * J * J;
         hipLaunchKernelGGL(sd::k_gru_dgx_sum, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, s, w.part, cnt, J * J, total,
                            dgx);
-        GT_HIP(hipGetLastError());
+        SD_HIP(hipGetLastError());
     }
     if (dW_hh || db_hh) {
         // dW_hh = sum_{b,t} dc (x) h_{t-1}, db_hh = sum_{b,t} dc: the graph-linear's weight / bias
         // gradient over B T rows with an identity mixing matrix (one pass, fixed order)
         hipLaunchKernelGGL(sd::k_gru_identity, dim3((unsigned)((J * J + 255) / 256)), dim3(256), 0, s, w.ident, J);
-        GT_HIP(hipGetLastError());
+        SD_HIP(hipGetLastError());
         if (n_types > 0) {
             hipLaunchKernelGGL(sd::k_gru_write_types, dim3(1), dim3(64), 0, s, nt, J, w.types);
-            GT_HIP(hipGetLastError());
+            SD_HIP(hipGetLastError());
         }
         // (z feeds only dghat, which is not asked for; the entry still wants a non-null pointer)
         const int rc = sd_gl_train_backward(hprev, c, w.dc, W_hh, n_types > 0 ? w.types : nullptr, n_types, w.ident,
@@ -623,7 +617,7 @@ int sd_gx_table_forward(const float* G, const float* G_add, int32_t J, int32_t T
     if (!gxt) return sd::set_error(SD_E_INVALID, "sd_gx_table_forward: gxt is null");
     hipLaunchKernelGGL(sd::k_gxt_fwd, dim3((unsigned)J), dim3(64), 0, (hipStream_t)stream, G, G_add, J, T, normalize0, eps,
                        gxt);
-    GT_HIP(hipGetLastError());
+    SD_HIP(hipGetLastError());
     return SD_OK;
 }
 
@@ -637,7 +631,7 @@ int sd_gx_table_backward(const float* G, const float* G_add, const float* gxt, c
     if (!dG) return sd::set_error(SD_E_INVALID, "sd_gx_table_backward: dG is null");
     hipLaunchKernelGGL(sd::k_gxt_bwd, dim3((unsigned)J), dim3(64), 0, (hipStream_t)stream, G, G_add, gxt, dgxt, J, T,
                        normalize0, eps, dG, dG_add);
-    GT_HIP(hipGetLastError());
+    SD_HIP(hipGetLastError());
     return SD_OK;
 }
 

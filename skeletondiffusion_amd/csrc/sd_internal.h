@@ -177,29 +177,6 @@ hipError_t launch_copy_rows(float* dst, int64_t dst_rs, const float* src, int64_
 // row-blocked v4 activation layout -> row-major (rows, J, F)
 hipError_t launch_unblock(float* out, const float* in, int64_t rows, int J, int F, hipStream_t s);
 
-// evaluation metrics (sd_metrics.hip)
-hipError_t launch_pairwise(const float* x, int64_t nseq, int S, int64_t X, float* l1_mean, float* l2_mean,
-                           hipStream_t s);
-hipError_t launch_ade_fde(const float* pred, const float* target, int64_t nseq, int S, int T, int64_t F, float* ade,
-                          float* fde, float* per_sample_ade, float* per_sample_fde, hipStream_t s);
-hipError_t launch_mm_ade_fde(const float* pred, const float* gts, const int64_t* pair_seq, int64_t npairs,
-                             const int64_t* seq_off, int64_t nseq, int S, int T, int64_t F, float* pair_ade,
-                             float* pair_fde, float* mmade, float* mmfde, hipStream_t s);
-
-// best-of-k training relaxation (sd_metrics.hip; trainer.py:182-222)
-hipError_t launch_best_of_k(const float* sim, const float* loss, int64_t nseq, int k, int64_t* idx, float* sel,
-                            hipStream_t s);
-hipError_t launch_best_of_k_bwd(const float* dsel, const int64_t* idx, int64_t nseq, int k, float* dloss, hipStream_t s);
-hipError_t launch_pose_loss(const float* pred, const float* target, int64_t nseq, int S, int T, int J, int C, int mse,
-                            float* out, hipStream_t s);
-
-// best-sample selection (sd_metrics.hip; metrics/utils.py:12-30, multimodal.py:37-42): per (sequence,
-// sample) the mean per-joint L2 distance to the target, then per sequence the first minimum, its
-// distance and the gathered trajectory / its last tail_frames frames (each output but d nullable)
-hipError_t launch_best_sample(const float* pred, const float* target, int64_t nseq, int S, int T, int J,
-                              int tail_frames, float* d, float* min_out, int64_t* idx_out, float* best_out,
-                              float* tail_out, hipStream_t s);
-
 // plan-finalize helpers (one-time)
 hipError_t launch_sinusoidal(float* emb, int T, int dim, float neg_scale, hipStream_t s);
 hipError_t launch_linear(const float* x, int M, int K, const float* W, const float* b, int N,
@@ -207,6 +184,12 @@ hipError_t launch_linear(const float* x, int M, int K, const float* W, const flo
 hipError_t launch_ghat(const float* G, float* Ghat, int J, int normalize, hipStream_t s);
 // sets the thread-local message sd_last_error() returns; returns `code` (sd_plan.hip)
 int set_error(int code, const std::string& msg);
+// a HIP call in an entry point (a function returning an SD_E_* code): its failure is the function's
+#define SD_HIP(x)                                                                                          \
+    do {                                                                                                   \
+        hipError_t e_ = (x);                                                                               \
+        if (e_ != hipSuccess) return sd::set_error(SD_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
+    } while (0)
 hipError_t launch_fold_gain(const float* W, const float* g, float mult, float* out,
                             int64_t rows, int K, hipStream_t s);
 hipError_t launch_sigma(const float* logvar, float* sig, int64_t n, hipStream_t s);

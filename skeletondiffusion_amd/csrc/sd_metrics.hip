@@ -18,7 +18,9 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <string>
 
+#include "../../include/skeldiff.h"
 #include "sd_internal.h"
 
 namespace sd {
@@ -364,82 +366,120 @@ __global__ __launch_bounds__(256) void k_best_select(const float* __restrict__ p
 
 }  // namespace
 
-hipError_t launch_best_sample(const float* pred, const float* target, int64_t nseq, int S, int T, int J,
-                              int tail_frames, float* d, float* min_out, int64_t* idx_out, float* best_out,
-                              float* tail_out, hipStream_t s) {
-    if (nseq <= 0) return hipSuccess;
-    if (S < 1 || S > kMaxSamples || T < 1 || J < 1 || tail_frames < 0 || tail_frames > T || nseq > INT32_MAX || !d)
-        return hipErrorInvalidValue;
-    const int64_t pairs = nseq * S, N = (int64_t)T * J, L = 3 * N, Lt = 3 * (int64_t)tail_frames * J;
+}  // namespace sd
+
+// The entry points (include/skeldiff.h): argument checks, then the launches.
+extern "C" {
+using namespace sd;
+
+int sd_pairwise_distances(const float* x, int64_t nseq, int32_t samples, int64_t features, float* l1_mean,
+                          float* l2_mean, void* stream) {
+    if (nseq < 0 || samples < 2 || samples > kMaxSamples || features < 1)
+        return set_error(SD_E_INVALID, "pairwise distances: need 2..64 samples, features >= 1");
+    if (nseq == 0) return SD_OK;
+    if (!x) return set_error(SD_E_INVALID, "pairwise distances: null input");
+    hipLaunchKernelGGL(k_pairwise, dim3((unsigned)nseq), dim3(256), 0, (hipStream_t)stream, x, samples, features, l1_mean,
+                       l2_mean);
+    SD_HIP(hipGetLastError());
+    return SD_OK;
+}
+
+int sd_ade_fde(const float* pred, const float* target, int64_t nseq, int32_t samples, int32_t frames,
+               int64_t features, float* ade, float* fde, float* per_sample_ade, float* per_sample_fde, void* stream) {
+    if (nseq < 0 || samples < 1 || samples > kMaxSamples || frames < 1 || features < 1)
+        return set_error(SD_E_INVALID, "ade/fde: need 1..64 samples, frames >= 1, features >= 1");
+    if (nseq == 0) return SD_OK;
+    if (!pred || !target) return set_error(SD_E_INVALID, "ade/fde: null input");
+    hipLaunchKernelGGL(k_ade_fde, dim3((unsigned)nseq), dim3(256), 0, (hipStream_t)stream, pred, target, samples, frames,
+                       features, ade, fde, per_sample_ade, per_sample_fde, (const int64_t*)nullptr);
+    SD_HIP(hipGetLastError());
+    return SD_OK;
+}
+
+int sd_mm_ade_fde(const float* pred, const float* gts, const int64_t* pair_seq, int64_t npairs,
+                  const int64_t* seq_offsets, int64_t nseq, int32_t samples, int32_t frames, int64_t features,
+                  float* pair_ade, float* pair_fde, float* mmade, float* mmfde, void* stream) {
+    if (nseq < 0 || npairs < 0 || samples < 1 || samples > kMaxSamples || frames < 1 || features < 1)
+        return set_error(SD_E_INVALID, "mmade/mmfde: need 1..64 samples, frames >= 1, features >= 1");
+    if (nseq == 0) return SD_OK;
+    if (!seq_offsets || (npairs > 0 && (!pred || !gts || !pair_seq)) || (mmade && !pair_ade) || (mmfde && !pair_fde))
+        return set_error(SD_E_INVALID, "mmade/mmfde: null input (pair outputs are required for the means)");
+    hipStream_t s = (hipStream_t)stream;
+    if (npairs > 0)
+        hipLaunchKernelGGL(k_ade_fde, dim3((unsigned)npairs), dim3(256), 0, s, pred, gts, samples, frames, features, pair_ade,
+                           pair_fde, (float*)nullptr, (float*)nullptr, pair_seq);
+    const dim3 g((unsigned)((nseq + 255) / 256));
+    if (mmade) hipLaunchKernelGGL(k_segment_mean, g, dim3(256), 0, s, pair_ade, seq_offsets, nseq, mmade);
+    if (mmfde) hipLaunchKernelGGL(k_segment_mean, g, dim3(256), 0, s, pair_fde, seq_offsets, nseq, mmfde);
+    SD_HIP(hipGetLastError());
+    return SD_OK;
+}
+
+// best-of-k training relaxation (trainer.py:182-222)
+int sd_best_of_k(const float* sim, const float* loss, int64_t nseq, int32_t k, int64_t* idx_out, float* loss_out,
+                 void* stream) {
+    if (nseq < 0 || k < 1) return set_error(SD_E_INVALID, "best_of_k: nseq >= 0, k >= 1");
+    if (nseq == 0) return SD_OK;
+    if (!loss || (!idx_out && !loss_out)) return set_error(SD_E_INVALID, "best_of_k: null buffer");
+    hipLaunchKernelGGL(k_best_of_k, dim3((unsigned)((nseq + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       sim ? sim : loss, loss, nseq, k, idx_out, loss_out);
+    SD_HIP(hipGetLastError());
+    return SD_OK;
+}
+
+int sd_best_of_k_backward(const float* dloss_sel, const int64_t* idx, int64_t nseq, int32_t k, float* dloss,
+                          void* stream) {
+    if (nseq < 0 || k < 1) return set_error(SD_E_INVALID, "best_of_k_backward: nseq >= 0, k >= 1");
+    if (nseq == 0) return SD_OK;
+    if (!dloss_sel || !idx || !dloss) return set_error(SD_E_INVALID, "best_of_k_backward: null buffer");
+    hipLaunchKernelGGL(k_best_of_k_bwd, dim3((unsigned)((nseq * k + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       dloss_sel, idx, nseq, k, dloss);
+    SD_HIP(hipGetLastError());
+    return SD_OK;
+}
+
+int sd_pose_loss(const float* pred, const float* target, int64_t nseq, int32_t samples, int32_t frames,
+                 int32_t joints, int32_t dims, int32_t mse, float* per_sample, void* stream) {
+    if (nseq < 0 || samples < 1 || frames < 1 || joints < 1 || dims < 1)
+        return set_error(SD_E_INVALID, "pose_loss: samples, frames, joints, dims >= 1");
+    if (nseq == 0) return SD_OK;
+    if (!pred || !target || !per_sample) return set_error(SD_E_INVALID, "pose_loss: null buffer");
+    hipLaunchKernelGGL(k_pose_loss, dim3((unsigned)((nseq * samples + 3) / 4)), dim3(256), 0, (hipStream_t)stream, pred,
+                       target, nseq, samples, frames, joints, dims, (int)(mse != 0), per_sample);
+    SD_HIP(hipGetLastError());
+    return SD_OK;
+}
+
+// best-sample selection (metrics/utils.py:12-30, multimodal.py:37-42): per (sequence, sample) the mean
+// per-joint L2 distance to the target, then per sequence the first minimum, its distance and the
+// gathered trajectory / its last tail_frames frames (each output but per_sample nullable)
+int sd_best_sample(const float* pred, const float* target, int64_t nseq, int32_t samples, int32_t frames,
+                   int32_t joints, int32_t coords, int32_t tail_frames, float* per_sample, float* min_out,
+                   int64_t* idx_out, float* best_out, float* tail_out, void* stream) {
+    if (nseq < 0 || nseq > INT32_MAX) return set_error(SD_E_INVALID, "best_sample: nseq must be in 0..2^31-1");
+    if (samples < 1 || samples > kMaxSamples) return set_error(SD_E_INVALID, "best_sample: samples must be in 1..64");
+    if (coords != 3) return set_error(SD_E_INVALID, "best_sample: coords must be 3");
+    if (frames < 1) return set_error(SD_E_INVALID, "best_sample: frames must be >= 1");
+    if (joints < 1) return set_error(SD_E_INVALID, "best_sample: joints must be >= 1");
+    if (tail_frames < 0 || tail_frames > frames) return set_error(SD_E_INVALID, "best_sample: tail_frames must be in 0..frames");
+    if (tail_out && tail_frames == 0) return set_error(SD_E_INVALID, "best_sample: tail_out given with tail_frames = 0");
+    if (nseq == 0) return SD_OK;
+    if (!pred) return set_error(SD_E_INVALID, "best_sample: pred is null");
+    if (!target) return set_error(SD_E_INVALID, "best_sample: target is null");
+    if (!per_sample) return set_error(SD_E_INVALID, "best_sample: per_sample is required (it is the workspace)");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t pairs = nseq * samples, N = (int64_t)frames * joints, L = 3 * N, Lt = 3 * (int64_t)tail_frames * joints;
     hipLaunchKernelGGL(k_sample_dist, dim3((unsigned)std::min(pairs, (int64_t)1 << 30)), dim3(256), 0, s, pred, target, pairs,
-                       S, N, d);
-    if (!tail_frames) tail_out = nullptr;
+                       samples, N, per_sample);
     if (min_out || idx_out || best_out || tail_out) {
         // 2 quads per thread and share; the copies of one sequence are at most a few hundred KB
         const int64_t span = std::max(best_out ? L : (int64_t)0, tail_out ? Lt : (int64_t)0);
         const unsigned shares = (unsigned)std::min(std::max((span + 2047) / 2048, (int64_t)1), (int64_t)32);
-        hipLaunchKernelGGL(k_best_select, dim3((unsigned)nseq, shares), dim3(256), 0, s, pred, d, S, L, Lt, min_out,
-                           idx_out, best_out, tail_out);
+        hipLaunchKernelGGL(k_best_select, dim3((unsigned)nseq, shares), dim3(256), 0, s, pred, per_sample, samples, L, Lt,
+                           min_out, idx_out, best_out, tail_out);
     }
-    return hipGetLastError();
+    SD_HIP(hipGetLastError());
+    return SD_OK;
 }
 
-hipError_t launch_best_of_k(const float* sim, const float* loss, int64_t nseq, int k, int64_t* idx, float* sel,
-                            hipStream_t s) {
-    if (nseq <= 0) return hipSuccess;
-    if (k < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_best_of_k, dim3((unsigned)((nseq + 255) / 256)), dim3(256), 0, s, sim ? sim : loss, loss,
-                       nseq, k, idx, sel);
-    return hipGetLastError();
-}
-
-hipError_t launch_best_of_k_bwd(const float* dsel, const int64_t* idx, int64_t nseq, int k, float* dloss,
-                                hipStream_t s) {
-    const int64_t n = nseq * k;
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_best_of_k_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dsel, idx, nseq, k, dloss);
-    return hipGetLastError();
-}
-
-hipError_t launch_pose_loss(const float* pred, const float* target, int64_t nseq, int S, int T, int J, int C, int mse,
-                            float* out, hipStream_t s) {
-    const int64_t waves = nseq * S;
-    if (waves <= 0) return hipSuccess;
-    if (T < 1 || J < 1 || C < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_pose_loss, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, pred, target, nseq, S, T, J, C,
-                       mse, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_pairwise(const float* x, int64_t nseq, int S, int64_t X, float* l1_mean, float* l2_mean,
-                           hipStream_t s) {
-    if (nseq <= 0) return hipSuccess;
-    if (S < 2 || S > kMaxSamples || X <= 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_pairwise, dim3((unsigned)nseq), dim3(256), 0, s, x, S, X, l1_mean, l2_mean);
-    return hipGetLastError();
-}
-
-hipError_t launch_ade_fde(const float* pred, const float* target, int64_t nseq, int S, int T, int64_t F, float* ade,
-                          float* fde, float* per_sample_ade, float* per_sample_fde, hipStream_t s) {
-    if (nseq <= 0) return hipSuccess;
-    if (S < 1 || S > kMaxSamples || T < 1 || F <= 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_ade_fde, dim3((unsigned)nseq), dim3(256), 0, s, pred, target, S, T, F, ade, fde,
-                       per_sample_ade, per_sample_fde, (const int64_t*)nullptr);
-    return hipGetLastError();
-}
-
-hipError_t launch_mm_ade_fde(const float* pred, const float* gts, const int64_t* pair_seq, int64_t npairs,
-                             const int64_t* seq_off, int64_t nseq, int S, int T, int64_t F, float* pair_ade,
-                             float* pair_fde, float* mmade, float* mmfde, hipStream_t s) {
-    if (nseq <= 0) return hipSuccess;
-    if (S < 1 || S > kMaxSamples || T < 1 || F <= 0 || npairs < 0) return hipErrorInvalidValue;
-    if (npairs > 0)
-        hipLaunchKernelGGL(k_ade_fde, dim3((unsigned)npairs), dim3(256), 0, s, pred, gts, S, T, F, pair_ade, pair_fde,
-                           (float*)nullptr, (float*)nullptr, pair_seq);
-    const dim3 g((unsigned)((nseq + 255) / 256));
-    if (mmade) hipLaunchKernelGGL(k_segment_mean, g, dim3(256), 0, s, pair_ade, seq_off, nseq, mmade);
-    if (mmfde) hipLaunchKernelGGL(k_segment_mean, g, dim3(256), 0, s, pair_fde, seq_off, nseq, mmfde);
-    return hipGetLastError();
-}
-
-}  // namespace sd
+}  // extern "C"

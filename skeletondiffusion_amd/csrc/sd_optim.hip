@@ -162,12 +162,6 @@ unsigned grid_of(const OptBatch& b) {
 }  // namespace optim
 }  // namespace sd
 
-#define OPT_HIP(x)                                                                                    \
-    do {                                                                                              \
-        hipError_t e_ = (x);                                                                          \
-        if (e_ != hipSuccess) return sd::set_error(SD_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 namespace {
 int bad(const char* fn, const std::string& what) { return sd::set_error(SD_E_INVALID, std::string(fn) + ": " + what); }
 }  // namespace
@@ -204,10 +198,10 @@ int sd_optim_grad_norm(const float* const* grads, const int64_t* numel, int32_t 
         build_batches(numel, n_tensors, [&](int i, OptTensor* t) { t->g = const_cast<float*>(grads[i]); });
     for (const OptBatch& b : batches) {
         hipLaunchKernelGGL(k_opt_norm, dim3(grid_of(b)), dim3(kThreads), 0, s, b, partials);
-        OPT_HIP(hipGetLastError());
+        SD_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(k_opt_norm_final, dim3(1), dim3(kThreads), 0, s, partials, chunks, max_norm, norm_coef);
-    OPT_HIP(hipGetLastError());
+    SD_HIP(hipGetLastError());
     return SD_OK;
 }
 
@@ -258,7 +252,7 @@ int sd_optim_adam_step(const sd_optim_param* params, int32_t n_tensors, double b
     hipStream_t s = (hipStream_t)stream;
     for (const OptBatch& b : batches) {
         hipLaunchKernelGGL(k_opt_step, dim3(grid_of(b)), dim3(kThreads), 0, s, b, call, coef);
-        OPT_HIP(hipGetLastError());
+        SD_HIP(hipGetLastError());
     }
     return SD_OK;
 }
@@ -285,7 +279,7 @@ int sd_optim_ema_update(float* const* ema, const float* const* params, const int
     hipStream_t s = (hipStream_t)stream;
     for (const OptBatch& b : batches) {
         hipLaunchKernelGGL(k_opt_ema, dim3(grid_of(b)), dim3(kThreads), 0, s, b, weight);
-        OPT_HIP(hipGetLastError());
+        SD_HIP(hipGetLastError());
     }
     return SD_OK;
 }

@@ -16,6 +16,7 @@
 
 #include "../../include/skeldiff.h"
 #include "sd_internal.h"
+#include "sd_workspace.h"
 
 namespace {
 
@@ -31,12 +32,6 @@ int fail(int code, const std::string& msg) {
 int sd::set_error(int code, const std::string& msg) { return fail(code, msg); }
 
 namespace {
-
-#define SD_HIP(x)                                                                              \
-    do {                                                                                       \
-        hipError_t e_ = (x);                                                                   \
-        if (e_ != hipSuccess) return fail(SD_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 struct Slot {
     std::string name;
@@ -58,6 +53,15 @@ struct GL {
     sd::SplitW split_bf;         // bf16 fragments of wuse (precision mode 2)
 };
 
+// The options that choose a plan's kernels (sd_plan_set_option SD_OPT_KERNEL_VARIANT, _GL4_TILE,
+// _GL4_STAGING, _SPLIT_ROUTE, _UPDATE_KERNEL, _V5_MIX, _ATTENTION; 0 = auto).  The plan holds one, a
+// captured graph's key the one it was captured under, and gl_args / run_update read the kernels'
+// selection from it: an option added here reaches the key with it.
+struct KernelOpts {
+    int32_t variant, gl4_cfg, gl4_stage, split, upd_elem, v5_valu, attn_tail;
+};
+
+// compared as bytes: sd_sample_loop zeroes it before filling it
 struct GraphKey {
     int64_t rows;
     const void* ptrs[10];
@@ -65,7 +69,7 @@ struct GraphKey {
     int32_t flags;
     int32_t chains;
     int32_t prec;
-    int32_t variant, gl4_cfg, gl4_stage, split, upd_elem, v5_valu, attn_tail;  // the plan's kernel options at capture time
+    KernelOpts opts;  // at capture time
     void* stream;
     bool operator<(const GraphKey& o) const { return std::memcmp(this, &o, sizeof(GraphKey)) < 0; }
 };
@@ -112,15 +116,13 @@ struct sd_plan {
     bool fuse_ok = false;  // to_qkv + attention fusable (v4 split weights, J <= 17 or 21, dim_head 32)
     bool blk_ok = false;   // every layer on v4 with row-blocked intermediate activations
     int prec = 0;          // sd_plan_set_precision: 0 f32-accurate, 1 half (f16 products)
-    // kernel options (sd_plan_set_option); 0 = auto, the only way a plan's kernels are chosen
-    int variant = 0, gl4_cfg = 0, gl4_stage = 0, split = 0, chains = 0;
-    int upd_elem = 0;  // SD_OPT_UPDATE_KERNEL: 1 = the element-per-thread update forms
-    int v5_valu = 0;   // SD_OPT_V5_MIX: 1 = the VALU mixing pass of v5
-    int attn_tail = 0;  // SD_OPT_ATTENTION: 0 auto (= 2 where it applies), 2 k_attention_mix, 3 separate mixing pass
-    bool fuse_attention_now() const { return fuse_ok && (variant == 0 || variant == 4); }
+    KernelOpts opts{};  // the only way a plan's kernels are chosen
+    int chains = 0;     // SD_OPT_ROW_CHAINS
+    bool fuse_attention_now() const { return fuse_ok && (opts.variant == 0 || opts.variant == 4); }
     // SD_OPT_ATTENTION 2 where it applies: the v5 route's to_qkv mixing inside the attention kernel
     bool attn_mix_now() const {
-        return (attn_tail == 0 || attn_tail == 2) && J >= 49 && J <= 52 && d.attn_dim_head == 32 && (variant == 0 || variant == 5) && prec != 2;
+        return (opts.attn_tail == 0 || opts.attn_tail == 2) && J >= 49 && J <= 52 && d.attn_dim_head == 32 &&
+               (opts.variant == 0 || opts.variant == 5) && prec != 2;
     }
     bool blocked_now() const { return blk_ok && fuse_attention_now() && prec != 2; }
     std::vector<void*> allocs;
@@ -149,7 +151,7 @@ struct sd_plan {
     std::mutex gmu;
     std::map<GraphKey, std::shared_ptr<GraphSet>> graphs;  // one graph per row chain
     // row chains (record_loop): auxiliary streams + fork/join events, created on first use
-    static constexpr int kMaxChains = 8;
+    static constexpr int kMaxChains = sd::kMaxChains;
     std::mutex cmu;
     std::atomic<int> last_chains{0};  // SD_OPT_LAST_CHAINS
     std::atomic<unsigned> last_route{0};  // SD_OPT_LAST_ROUTE
@@ -195,6 +197,7 @@ struct sd_plan {
         return g;
     }
     const float* ptr(int slot) const { return slot < 0 ? nullptr : slots[slot].dev; }
+    sd::WsDims ws_dims() const { return sd::WsDims{J, H, D, O, hid, d.use_attention != 0}; }
 };
 
 namespace {
@@ -231,95 +234,94 @@ int dalloc(sd_plan* p, T** out, size_t n) {
     return SD_OK;
 }
 
-// workspace carve (all offsets 256-B aligned)
+// One view of the workspace (sd_workspace.h has the layout): a whole call's, or a row chain's.
 struct WS {
-    uint64_t* rng;      // {seed, row0} of the device noise (graph replays); rng + 4: status word
+    uint64_t* rng;  // {seed, row0} of the device noise (graph replays), then the status word
     float *x, *r, *h, *qkv, *o, *res, *x0, *img0, *img1;
+    int64_t zs_cap;  // floats of qkv the view's kernels may use (GLArgs::zs_cap)
 };
+// the float buffers in the order of the layout's table (sd::WsBuf; rng apart)
+constexpr float* WS::*kWsMember[sd::kWsBufs] = {nullptr,  &WS::x,  &WS::r,    &WS::h,   &WS::qkv,
+                                                &WS::o,   &WS::res, &WS::x0, &WS::img0, &WS::img1};
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// floats per (row, node) of the qkv buffer: to_qkv's output, and the split route's pre-mix Y scratch
-// of every graph-linear outside the attention block (the widest layer's N: at least H)
-int64_t qkv_width(const sd_plan* p) {
-    return std::max<int64_t>({p->d.use_attention ? 3 * (int64_t)p->hid : 0, (int64_t)p->H, (int64_t)p->O});
+// the view of `rows` rows carved from base (256-B aligned)
+WS ws_carve_view(const sd_plan* p, int64_t rows, char* base) {
+    const sd::WsDims d = p->ws_dims();
+    const sd::WsCarve c = sd::ws_carve(d, rows);
+    WS w{};
+    w.rng = reinterpret_cast<uint64_t*>(base + c.off[sd::kWsRng]);
+    for (int b = sd::kWsRng + 1; b < sd::kWsBufs; ++b) w.*kWsMember[b] = reinterpret_cast<float*>(base + c.off[b]);
+    w.zs_cap = sd::ws_cap(d, sd::kWsQkv, rows);
+    return w;
 }
-
-size_t carve(const sd_plan* p, int64_t rows, char* base, WS* w) {
-    const size_t f = sizeof(float);
-    const size_t rp = (size_t)((rows + 31) / 32 * 32);  // activations: padded to the 32-row blocks of the v4 layout
-    const size_t nH = rp * p->J * p->H * f;
-    const size_t nQ = rp * p->J * qkv_width(p) * f;
-    const size_t nO = rp * p->J * (p->d.use_attention ? p->hid : p->H) * f;  // no attention: GL output
-    const size_t nD = (size_t)rows * p->J * p->D * f;
-    size_t off = 0;
-    auto take = [&](size_t n) {
-        char* q = base ? base + off : nullptr;
-        off += align256(n);
-        return q;
-    };
-    WS tmp;
-    WS& W = w ? *w : tmp;
-    W.rng = (uint64_t*)take(64);
-    W.x = (float*)take(nH);
-    W.r = (float*)take(nH);
-    W.h = (float*)take(nH);
-    W.qkv = (float*)take(nQ);
-    W.o = (float*)take(nO);
-    W.res = (float*)take(nH);
-    W.x0 = (float*)take(nD);
-    W.img0 = (float*)take(nD);
-    W.img1 = (float*)take(nD);
-    return off;
+// the view of a row chain: rows [r0, r0 + n) of w
+WS ws_chain_view(const sd_plan* p, const WS& w, int64_t r0, int64_t n) {
+    const sd::WsDims d = p->ws_dims();
+    WS o = w;
+    for (int b = sd::kWsRng + 1; b < sd::kWsBufs; ++b) o.*kWsMember[b] += sd::ws_shift(d, b, r0);
+    o.zs_cap = sd::ws_cap(d, sd::kWsQkv, n);
+    return o;
 }
 
 // the workspace's status word (range-guard flags, sd_workspace_status)
-unsigned* ws_status(const WS& w) { return reinterpret_cast<unsigned*>(w.rng + 4); }
+unsigned* ws_status(const WS& w) { return reinterpret_cast<unsigned*>(reinterpret_cast<char*>(w.rng) + sd::kWsStatusByte); }
 // entry points zero the status word
 int ws_reset(const WS& w, hipStream_t s) {
     SD_HIP(hipMemsetAsync(ws_status(w), 0, sizeof(unsigned), s));
     return SD_OK;
 }
 
-sd::GLArgs gl_args(const sd_plan* p, const GL& g, const float* x1, int x1_div, const float* x2,
-                   const float* film, const float* res, float* out, int64_t rows) {
+// The fields every graph-linear launch fills the same way, the plan's (gl_args) and the sd_test_*
+// hooks': operands with their row strides, the shape, and the per-node weight rows from J node
+// types.  ntypes = 0: as many types as the array names.  Optional operands (x2, film, res), the
+// activation and the layouts are the caller's to set by name.
+struct GLShape {
+    int J, K1, K2, N;
+};
+template <typename T>
+sd::GLArgs gl_build(const GLShape& sh, const float* x1, float* out, int64_t rows, const T* types, int ntypes) {
     sd::GLArgs a{};
     a.x1 = x1;
-    a.K1 = g.K1;
-    a.x1_rs = (int64_t)p->J * g.K1;
-    a.x1_div = x1_div;
-    a.x2 = x2;
-    a.K2 = g.K2;
-    a.x2_rs = (int64_t)p->J * g.K2;
+    a.K1 = sh.K1;
+    a.x1_rs = (int64_t)sh.J * sh.K1;
+    a.x1_div = 1;
+    a.K2 = sh.K2;
+    a.x2_rs = (int64_t)sh.J * sh.K2;
+    a.res_rs = (int64_t)sh.J * sh.N;
+    a.out = out;
+    a.out_rs = (int64_t)sh.J * sh.N;
+    a.B = rows;
+    a.N = sh.N;
+    a.J = sh.J;
+    a.ntypes = std::max(ntypes, 1);
+    for (int j = 0; j < sh.J; ++j) {
+        a.wrow[j] = (int)types[j] * sh.N;
+        a.ntype[j] = (int)types[j];
+        if (!ntypes) a.ntypes = std::max(a.ntypes, (int)types[j] + 1);
+    }
+    return a;
+}
+void gl_set_split(sd::GLArgs& a, const sd::SplitW& sw) {
+    a.wsp = sw.w;
+    a.wsp_nct = sw.nct;
+    a.wsp_unscale = sw.unscale;
+}
+
+// layer g of the plan reading x1, writing out
+sd::GLArgs gl_args(const sd_plan* p, const GL& g, const float* x1, float* out, int64_t rows) {
+    sd::GLArgs a = gl_build(GLShape{p->J, g.K1, g.K2, g.N}, x1, out, rows, p->types.data(), p->ntypes);
     a.W = g.wuse;
     a.bias = p->ptr(g.b);
     a.ln_w = p->ptr(g.lnw);
     a.ln_b = p->ptr(g.lnb);
     a.G = g.ghat;
-    a.film = film;
-    a.res = res;
-    a.res_rs = (int64_t)p->J * g.N;
-    a.out = out;
-    a.out_rs = (int64_t)p->J * g.N;
-    a.B = rows;
-    a.N = g.N;
-    a.J = p->J;
-    a.act = 0;
-    a.ntypes = p->ntypes;
-    for (int j = 0; j < p->J; ++j) {
-        a.wrow[j] = p->types[j] * g.N;
-        a.ntype[j] = p->types[j];
-    }
-    const sd::SplitW& sw = p->prec == 2 ? g.split_bf : g.split;  // bf16 mode: the bf16 fragments
-    a.wsp = sw.w;
-    a.wsp_nct = sw.nct;
-    a.wsp_unscale = sw.unscale;
+    gl_set_split(a, p->prec == 2 ? g.split_bf : g.split);  // bf16 mode: the bf16 fragments
     a.prec = p->prec;
-    a.variant = p->variant;
-    a.gl4_cfg = p->gl4_cfg;
-    a.gl4_stage = p->gl4_stage;
-    a.split = p->split;
-    a.v5_valu = p->v5_valu;
+    a.variant = p->opts.variant;
+    a.gl4_cfg = p->opts.gl4_cfg;
+    a.gl4_stage = p->opts.gl4_stage;
+    a.split = p->opts.split;
+    a.v5_valu = p->opts.v5_valu;
     return a;
 }
 
@@ -342,19 +344,43 @@ struct Prof {
     }
 };
 
-#define SD_LAUNCH(prof, c, expr)                                                               \
-    do {                                                                                       \
-        if (prof && prof->pre(c, s)) return fail(SD_E_HIP, "hipEventRecord failed");          \
-        SD_HIP(expr);                                                                          \
-        if (prof && prof->post(s)) return fail(SD_E_HIP, "hipEventRecord failed");            \
+// What a launch sequence runs on: the plan, its view of the workspace and the rows there, the
+// stream, and what the sampling call around it looks like.
+struct Call {
+    const sd_plan* p;
+    WS w;
+    int64_t rows;
+    hipStream_t s;
+    Prof* prof = nullptr;           // sd_profile_step
+    int64_t route_rows = 0;         // rows of the whole sampling call, all row chains (GLArgs::route_rows); 0: rows
+    int64_t cond_phase = 0;         // row 0 here is row cond_phase of a cond_repeat group (row chains)
+    int tile_hint = 0;              // GLArgs::tile_hint
+    int lat_bf16 = 0;               // x_t and x0 hold bf16 (precision 2, between the steps of sd_sample_loop)
+    float* const* trace = nullptr;  // sd_denoiser_trace
+};
+
+// One launch (or a launch and its fallback) between the profiler's events.  The launch's own error
+// is handed back: hipErrorNotSupported is a route saying that it does not apply.
+template <typename F>
+int launch_timed(const Call& c, int cls, hipError_t* e, F launch) {
+    if (c.prof && c.prof->pre(cls, c.s)) return fail(SD_E_HIP, "hipEventRecord failed");
+    *e = launch();
+    if (c.prof && c.prof->post(c.s)) return fail(SD_E_HIP, "hipEventRecord failed");
+    return SD_OK;
+}
+#define SD_LAUNCH(c, cls, expr)                                                                               \
+    do {                                                                                                      \
+        hipError_t le_;                                                                                       \
+        if (int lrc_ = launch_timed(c, cls, &le_, [&] { return (expr); })) return lrc_;                       \
+        if (le_ != hipSuccess) return fail(SD_E_HIP, std::string(#expr) + ": " + hipGetErrorString(le_));     \
     } while (0)
 
-// Denoiser.forward (generator.py:86-107) for `rows` rows at time t.
-// cond_phase: row 0 of this call is row cond_phase of a cond_repeat group (row chains)
-int run_denoiser(const sd_plan* p, const float* x_t, const float* x_cond, int64_t cond_repeat,
-                 int t, float* x0_out, int64_t rows, const WS& w, hipStream_t s, Prof* prof = nullptr,
-                 int64_t cond_phase = 0, int tile_hint = 0, float* const* trace = nullptr,
-                 int xt_bf16 = 0, int x0_bf16 = 0, int64_t route_rows = 0) {
+// Denoiser.forward (generator.py:86-107) for c.rows rows at time t.
+int run_denoiser(const Call& c, const float* x_t, const float* x_cond, int64_t cond_repeat, int t, float* x0_out) {
+    const sd_plan* p = c.p;
+    const WS& w = c.w;
+    const hipStream_t s = c.s;
+    const int64_t rows = c.rows;
     const int H = p->H;
     // v4 path: every intermediate activation in the row-blocked layout (coalesced x fragments);
     // the denoiser's inputs (x_t, x_cond) and output (x0) stay row-major
@@ -365,29 +391,29 @@ int run_denoiser(const sd_plan* p, const float* x_t, const float* x_cond, int64_
     const bool bf = p->prec == 2;
     auto bfl = [&](const float* q) -> int {
         if (!q) return 0;
-        if (q == x_t) return xt_bf16;
-        if (q == x0_out) return x0_bf16;
+        if (q == x_t || q == x0_out) return c.lat_bf16;
         return bf && (q == w.r || q == w.x || q == w.h || q == w.res || (!p->d.use_attention && q == w.o));
     };
     // sd_denoiser_trace: block outputs (rows, J, H) row-major, in the reference's module order
     int ntr = 0;
     auto record = [&](const float* buf) -> int {
-        if (!trace) return SD_OK;
-        float* dst = trace[ntr++];
+        if (!c.trace) return SD_OK;
+        float* dst = c.trace[ntr++];
         if (B) SD_HIP(sd::launch_unblock(dst, buf, rows, p->J, H, s));
         else SD_HIP(sd::launch_convert_rows(dst, 0, (int64_t)p->J * H, buf, bfl(buf), (int64_t)p->J * H, rows,
                                             (int64_t)p->J * H, s));
         return SD_OK;
     };
-    // split-route / v5 scratch (pre-mix activations; v5: of layers whose residual aliases their
-    // output): the qkv buffer, dead outside the attention block, as wide as the widest layer
-    const int64_t zs_cap = (rows + 31) / 32 * 32 * p->J * qkv_width(p);
-    auto lay = [B, tile_hint, &w, zs_cap, &bfl, route_rows](sd::GLArgs& g, int in, int res, int out) {
+    // layer g reading x1 and writing out; x2, film, res and act are set by name on the result, then
+    // lay() gives it the call's part.  zs: the split-route / v5 scratch (pre-mix activations; v5: of
+    // layers whose residual aliases their output) is the qkv buffer, dead outside the attention block
+    auto layer = [&](const GL& g, const float* x1, float* out) { return gl_args(p, g, x1, out, rows); };
+    auto lay = [&](sd::GLArgs& g, int in, int res, int out) {
         g.status = ws_status(w);
-        g.route_rows = route_rows;
+        g.route_rows = c.route_rows;
         g.zs = w.qkv;
-        g.zs_cap = zs_cap;
-        g.tile_hint = tile_hint;
+        g.zs_cap = w.zs_cap;
+        g.tile_hint = c.tile_hint;
         g.x1_blk = g.x2_blk = B & in;
         g.res_blk = B & res;
         g.out_blk = B & out;
@@ -401,29 +427,32 @@ int run_denoiser(const sd_plan* p, const float* x_t, const float* x_cond, int64_
     // The init_lin output is `r` (generator.py:95, r = x.clone()); it is written to w.r and the
     // first ResnetBlock reads it from there and writes its result to w.x, so no copy is needed.
     if (p->C > 0) {
-        a = gl_args(p, p->init_lin, x_cond, (int)cond_repeat, x_t, nullptr, nullptr, w.r, rows);
-        a.x1_row0 = cond_phase;
+        a = layer(p->init_lin, x_cond, w.r);
+        a.x1_div = (int)cond_repeat;
+        a.x1_row0 = c.cond_phase;
+        a.x2 = x_t;
     } else {
-        a = gl_args(p, p->init_lin, x_t, 1, nullptr, nullptr, nullptr, w.r, rows);
+        a = layer(p->init_lin, x_t, w.r);
     }
     lay(a, 0, 0, 1);
-    SD_LAUNCH(prof, 0, sd::launch_graph_linear(a, false, s));
+    SD_LAUNCH(c, 0, sd::launch_graph_linear(a, false, s));
     int rc = record(w.r);
     if (rc) return rc;
 
     const int L = 2 * p->depth;
     for (int l = 0; l < L; ++l) {
-        const float* film = p->film + ((size_t)l * p->T + t) * 2 * H;
         const float* xin = (l == 0) ? w.r : w.x;
         // ResnetBlock: h = tanh(FiLM(GL1 x)); x = tanh(GL2 h) + x     (attention.py:96-102)
-        a = gl_args(p, p->r1[l], xin, 1, nullptr, film, nullptr, w.h, rows);
-        lay(a, 1, 1, 1);
+        a = layer(p->r1[l], xin, w.h);
+        a.film = p->film + ((size_t)l * p->T + t) * 2 * H;
         a.act = 1;
-        SD_LAUNCH(prof, 0, sd::launch_graph_linear(a, false, s));
-        a = gl_args(p, p->r2[l], w.h, 1, nullptr, nullptr, xin, w.x, rows);
         lay(a, 1, 1, 1);
+        SD_LAUNCH(c, 0, sd::launch_graph_linear(a, false, s));
+        a = layer(p->r2[l], w.h, w.x);
+        a.res = xin;
         a.act = 1;
-        SD_LAUNCH(prof, 0, sd::launch_graph_linear(a, false, s));
+        lay(a, 1, 1, 1);
+        SD_LAUNCH(c, 0, sd::launch_graph_linear(a, false, s));
         if ((rc = record(w.x))) return rc;
         if (!p->has_attn[l]) {
             if ((rc = record(w.x))) return rc;  // nn.Identity in place of the last attention
@@ -433,65 +462,70 @@ int run_denoiser(const sd_plan* p, const float* x_t, const float* x_cond, int64_
             // Residual(PreNorm(Attention)): x = to_out(attn(to_qkv(rmsnorm(x)))) + x
             // q * dim_head ** -0.5 (attention.py:114,128): Python double scalar cast to fp32
             const float qscale = (float)std::pow((double)p->d.attn_dim_head, -0.5);
-            hipError_t fused = hipErrorNotSupported;
+            hipError_t e = hipErrorNotSupported;
             if (p->fuse_attention_now()) {  // to_qkv + attention in one kernel, qkv stays on chip
-                a = gl_args(p, p->qkv[l], w.x, 1, nullptr, nullptr, nullptr, w.o, rows);
+                a = layer(p->qkv[l], w.x, w.o);
                 a.out_rs = (int64_t)p->J * p->hid;
                 a.attn_heads = p->d.attn_heads;
                 a.attn_scale = qscale;
                 lay(a, 1, 1, 1);
-                if (prof && prof->pre(0, s)) return fail(SD_E_HIP, "hipEventRecord failed");
-                fused = sd::launch_qkv_attention_v4(a, true, s);
-                if (fused != hipSuccess && fused != hipErrorNotSupported) SD_HIP(fused);
-                if (prof && prof->post(s)) return fail(SD_E_HIP, "hipEventRecord failed");
+                if ((rc = launch_timed(c, 0, &e, [&] { return sd::launch_qkv_attention_v4(a, true, s); }))) return rc;
+                if (e != hipErrorNotSupported) SD_HIP(e);
             }
-            if (fused == hipErrorNotSupported) {
+            if (e == hipErrorNotSupported) {
                 if (B) return fail(SD_E_INTERNAL, "row-blocked plan without the fused attention kernel");
-                a = gl_args(p, p->qkv[l], w.x, 1, nullptr, nullptr, nullptr, w.qkv, rows);
+                a = layer(p->qkv[l], w.x, w.qkv);
                 lay(a, 0, 0, 0);
                 // SD_OPT_ATTENTION 2: the GEMM phase alone, k_attention_mix mixes (else, or where
                 // the route cannot leave the pre-mix Y in qkv, the whole layer)
                 a.skip_mix = p->attn_mix_now() ? 1 : 0;
-                if (prof && prof->pre(0, s)) return fail(SD_E_HIP, "hipEventRecord failed");
-                hipError_t ge = sd::launch_graph_linear(a, true, s);
-                if (ge == hipErrorNotSupported && a.skip_mix) {
-                    a.skip_mix = 0;
-                    ge = sd::launch_graph_linear(a, true, s);
-                }
-                SD_HIP(ge);
-                if (prof && prof->post(s)) return fail(SD_E_HIP, "hipEventRecord failed");
+                rc = launch_timed(c, 0, &e, [&] {
+                    hipError_t ge = sd::launch_graph_linear(a, true, s);
+                    if (ge == hipErrorNotSupported && a.skip_mix) {
+                        a.skip_mix = 0;
+                        ge = sd::launch_graph_linear(a, true, s);
+                    }
+                    return ge;
+                });
+                if (rc) return rc;
+                SD_HIP(e);
                 sd::AttnArgs aa{w.qkv, w.o, rows, p->J, p->d.attn_heads, p->d.attn_dim_head, qscale,
                                 a.skip_mix ? a.G : nullptr};
-                SD_LAUNCH(prof, 1, sd::launch_attention(aa, s));
+                SD_LAUNCH(c, 1, sd::launch_attention(aa, s));
             }
-            a = gl_args(p, p->outp[l], w.o, 1, nullptr, nullptr, w.x, w.x, rows);
+            a = layer(p->outp[l], w.o, w.x);
+            a.res = w.x;
             lay(a, 1, 1, 1);
-            SD_LAUNCH(prof, 0, sd::launch_graph_linear(a, false, s));
+            SD_LAUNCH(c, 0, sd::launch_graph_linear(a, false, s));
         } else {
             // Residual(PreNorm(StaticGraphLinear)): x = GL(rmsnorm(x)) + x, written to the `o`
             // buffer (sized like x in this configuration: a graph-linear may not write its own
             // input, sibling column tiles still read it) and copied back as x
-            a = gl_args(p, p->qkv[l], w.x, 1, nullptr, nullptr, w.x, w.o, rows);
+            a = layer(p->qkv[l], w.x, w.o);
+            a.res = w.x;
             lay(a, 1, 1, 1);
-            SD_LAUNCH(prof, 0, sd::launch_graph_linear(a, true, s));
+            SD_LAUNCH(c, 0, sd::launch_graph_linear(a, true, s));
             const int64_t rp = B ? (rows + 31) / 32 * 32 : rows;
-            SD_LAUNCH(prof, 0, sd::launch_convert_rows(w.x, bfl(w.x), (int64_t)p->J * H, w.o, bfl(w.o), (int64_t)p->J * H, rp,
-                                                       (int64_t)p->J * H, s));
+            SD_LAUNCH(c, 0, sd::launch_convert_rows(w.x, bfl(w.x), (int64_t)p->J * H, w.o, bfl(w.o), (int64_t)p->J * H, rp,
+                                                    (int64_t)p->J * H, s));
         }
         if ((rc = record(w.x))) return rc;
     }
     // final_res_block on cat(x, r) (generator.py:104-106)
-    const float* film = p->film + ((size_t)L * p->T + t) * 2 * H;
-    a = gl_args(p, p->fres_res, w.x, 1, w.r, nullptr, nullptr, w.res, rows);
+    a = layer(p->fres_res, w.x, w.res);
+    a.x2 = w.r;
     lay(a, 1, 1, 1);
-    sd::GLArgs b1 = gl_args(p, p->r1[L], w.x, 1, w.r, film, nullptr, w.h, rows);
-    lay(b1, 1, 1, 1);
+    sd::GLArgs b1 = layer(p->r1[L], w.x, w.h);
+    b1.x2 = w.r;
+    b1.film = p->film + ((size_t)L * p->T + t) * 2 * H;
     b1.act = 1;
+    lay(b1, 1, 1, 1);
     // res_linear and block1 read the same input: on the tiled split route one GEMM-phase and one
     // mixing launch for both (sd_graph_linear_v4.hip, paired launch), else one layer after the other
     bool paired = false;
-    if (p->pair_ok && (p->variant == 0 || p->variant == 4)) {
-        sd::GLArgs pr = gl_args(p, p->fres_pair, w.x, 1, w.r, nullptr, nullptr, nullptr, rows);
+    if (p->pair_ok && (p->opts.variant == 0 || p->opts.variant == 4)) {
+        sd::GLArgs pr = layer(p->fres_pair, w.x, nullptr);
+        pr.x2 = w.r;
         lay(pr, 1, 1, 1);
         pr.bias = p->pair_bias;
         pr.pair_n = a.N;
@@ -501,58 +535,40 @@ int run_denoiser(const sd_plan* p, const float* x_t, const float* x_cond, int64_
         pa.zs_n = pb.zs_n = pr.N;
         pb.zs_c0 = a.N;
         if (sd::graph_linear_pair_ok(pr, pa, pb)) {
-            SD_LAUNCH(prof, 0, sd::launch_graph_linear_pair_v4(pr, pa, pb, s));
+            SD_LAUNCH(c, 0, sd::launch_graph_linear_pair_v4(pr, pa, pb, s));
             paired = true;
         }
     }
-    if (!paired) SD_LAUNCH(prof, 0, sd::launch_graph_linear(a, false, s));
-    if (!paired) SD_LAUNCH(prof, 0, sd::launch_graph_linear(b1, false, s));
-    a = gl_args(p, p->r2[L], w.h, 1, nullptr, nullptr, w.res, w.res, rows);
-    lay(a, 1, 1, 1);
+    if (!paired) SD_LAUNCH(c, 0, sd::launch_graph_linear(a, false, s));
+    if (!paired) SD_LAUNCH(c, 0, sd::launch_graph_linear(b1, false, s));
+    a = layer(p->r2[L], w.h, w.res);
+    a.res = w.res;
     a.act = 1;
-    SD_LAUNCH(prof, 0, sd::launch_graph_linear(a, false, s));
+    lay(a, 1, 1, 1);
+    SD_LAUNCH(c, 0, sd::launch_graph_linear(a, false, s));
     if ((rc = record(w.res))) return rc;
     // final_glin (generator.py:107)
-    a = gl_args(p, p->fglin, w.res, 1, nullptr, nullptr, nullptr, x0_out, rows);
+    a = layer(p->fglin, w.res, x0_out);
     lay(a, 1, 1, 0);
-    SD_LAUNCH(prof, 0, sd::launch_graph_linear(a, false, s));
+    SD_LAUNCH(c, 0, sd::launch_graph_linear(a, false, s));
     return SD_OK;
 }
 
-int run_update(const sd_plan* p, const float* x0, const float* xt, const float* eps,
-               int64_t eps_rs, int noise_mode, uint64_t seed, int64_t row0,
-               const uint64_t* rng_dev, int t, float* out, float* out2, int64_t out2_rs,
-               float* mean_out, int64_t mean_rs, float* noise_out, int64_t noise_rs, int64_t rows,
-               hipStream_t s, Prof* prof = nullptr, int64_t row_shift = 0, int x0_bf16 = 0, int xt_bf16 = 0,
-               int out_bf16 = 0, int clip = 1) {
-    sd::UpdArgs u{};
-    u.clip = clip;
-    u.x0_bf16 = x0_bf16;
-    u.xt_bf16 = xt_bf16;
-    u.out_bf16 = out_bf16;
-    u.x0 = x0;
-    u.xt = xt;
-    u.eps = eps;
-    u.eps_rs = eps_rs;
+// One posterior step.  u: the caller's part of the kernel's arguments, set by name -- x0 (the
+// Denoiser's output) and x_t in, x_{t-1} out, clip, the optional records with their row strides, and
+// the noise: given rows (eps) or Philox (seed / row0, or the workspace's rng block, and row_shift).
+// The plan's and the step's part is filled here.
+int run_update(const Call& c, int t, sd::UpdArgs u) {
+    const sd_plan* p = c.p;
+    u.x0_bf16 = u.xt_bf16 = c.lat_bf16;
     u.iso = p->d.isotropic;
     u.act = p->d.activation;
-    u.noise_mode = (t > 0) ? noise_mode : 0;
-    u.seed = seed;
-    u.row0 = row0;
+    u.noise_mode = t > 0 ? (u.eps ? 1 : 2) : 0;
     u.step = t;
-    u.rng_dev = rng_dev;
-    u.row_shift = row_shift;
-    u.out = out;
-    u.out2 = out2;
-    u.out2_rs = out2_rs;
-    u.mean_out = mean_out;
-    u.mean_rs = mean_rs;
-    u.noise_out = noise_out;
-    u.noise_rs = noise_rs;
-    u.B = rows;
+    u.B = c.rows;
     u.J = p->J;
     u.D = p->D;
-    u.elementwise = p->upd_elem == 1;
+    u.elementwise = p->opts.upd_elem == 1;
     if (p->d.isotropic) {
         u.c1s = p->iso_c1[t];
         u.c2s = p->iso_c2[t];
@@ -569,26 +585,46 @@ int run_update(const sd_plan* p, const float* x0, const float* xt, const float* 
         u.U = p->ptr(p->s_u);
         u.sig = p->sig + (size_t)t * p->J;
     }
-    SD_LAUNCH(prof, 2, sd::launch_update(u, s));
+    SD_LAUNCH(c, 2, sd::launch_update(u, c.s));
     return SD_OK;
+}
+
+// Every graph-linear of the plan, in the order sd_plan_finalize packs them: f(g) for each, stopping
+// at the first non-zero result.  The one enumeration of the layers (packing, the v4 / bf16 scans,
+// the FLOP count).  fres_pair is not in it: it is derived at finalize from fres_res and r1.back(),
+// which are, and owns no tensor, no G-hat and no FLOPs of its own.
+template <typename P, typename F>
+int for_each_gl(P* p, F f) {
+    int rc;
+    if ((rc = f(p->init_lin))) return rc;
+    for (auto& g : p->r1)
+        if ((rc = f(g))) return rc;
+    for (auto& g : p->r2)
+        if ((rc = f(g))) return rc;
+    for (size_t l = 0; l < p->qkv.size(); ++l) {
+        if (!p->has_attn[l]) continue;
+        if ((rc = f(p->qkv[l]))) return rc;
+        if (p->d.use_attention && (rc = f(p->outp[l]))) return rc;
+    }
+    if ((rc = f(p->fres_res))) return rc;
+    return f(p->fglin);
+}
+// whether every layer runs on the v4 kernels with the given weight fragments (f16 split, or bf16)
+bool all_gl_v4(const sd_plan* p, sd::SplitW GL::*frag) {
+    return !for_each_gl(p, [frag](const GL& g) { return (g.*frag).w && (g.K1 + g.K2) % 32 == 0 ? 0 : 1; });
 }
 
 // algorithmic FLOPs of one reverse step for `rows` rows: [graph-linear, attention, update]
 void step_flops(const sd_plan* p, int64_t rows, double* f) {
     const double J = p->J, R = (double)rows;
-    auto gl = [&](const GL& g) { return 2.0 * R * J * g.N * (g.K1 + g.K2) + 2.0 * R * J * J * g.N; };
-    f[0] = gl(p->init_lin) + gl(p->fres_res) + gl(p->fglin);
-    for (auto& g : p->r1) f[0] += gl(g);
-    for (auto& g : p->r2) f[0] += gl(g);
-    f[1] = 0.0;
-    for (size_t l = 0; l < p->has_attn.size(); ++l) {
-        if (!p->has_attn[l]) continue;
-        f[0] += gl(p->qkv[l]);
-        if (p->d.use_attention) {
-            f[0] += gl(p->outp[l]);
-            f[1] += 4.0 * R * J * J * p->d.attn_dim_head * p->d.attn_heads;  // QK^T and PV
-        }
-    }
+    f[0] = 0.0;
+    for_each_gl(p, [&](const GL& g) {
+        f[0] += 2.0 * R * J * g.N * (g.K1 + g.K2) + 2.0 * R * J * J * g.N;
+        return 0;
+    });
+    // QK^T and PV of every attention block
+    const double nattn = p->d.use_attention ? (double)std::count(p->has_attn.begin(), p->has_attn.end(), true) : 0.0;
+    f[1] = nattn * 4.0 * R * J * J * p->d.attn_dim_head * p->d.attn_heads;
     // C1 x0 + C2 x_t + U (sigma eps): three J x J products per latent column
     f[2] = p->d.isotropic ? 6.0 * R * J * p->D : 6.0 * R * J * J * p->D;
 }
@@ -632,7 +668,6 @@ int sd_plan_create(sd_plan** out, const sd_plan_desc* desc) {
         p->ntypes = desc->num_node_types;
     }
     const int J = p->J, H = p->H, hid = p->hid;
-    p->ntypes = desc->num_node_types > 0 ? desc->num_node_types : 1;
 
     // tensor registry in the reference layout (generator.py:30-84)
     const std::string m = "model.";
@@ -758,18 +793,7 @@ int sd_plan_finalize(sd_plan* p, void* stream_) {
         }
         return SD_OK;
     };
-    if ((rc = pack_gl(p->init_lin))) return rc;
-    for (auto& g : p->r1)
-        if ((rc = pack_gl(g))) return rc;
-    for (auto& g : p->r2)
-        if ((rc = pack_gl(g))) return rc;
-    for (size_t l = 0; l < p->qkv.size(); ++l) {
-        if (!p->has_attn[l]) continue;
-        if ((rc = pack_gl(p->qkv[l]))) return rc;
-        if (p->d.use_attention && (rc = pack_gl(p->outp[l]))) return rc;
-    }
-    if ((rc = pack_gl(p->fres_res))) return rc;
-    if ((rc = pack_gl(p->fglin))) return rc;
+    if ((rc = for_each_gl(p, pack_gl))) return rc;
     {
         // the pair's B fragments: per (type, chunk) the column tiles of res_linear, then block1's
         // (make_split_weights layout [type][chunk][tile][1024 halves]; unpadded: nct * 32 == N), each
@@ -810,15 +834,7 @@ int sd_plan_finalize(sd_plan* p, void* stream_) {
     for (size_t l = 0; l < p->qkv.size(); ++l)
         if (p->has_attn[l] && !p->qkv[l].split.w) p->fuse_ok = false;
     // row-blocked activations need every graph-linear on v4 (split weights, K multiple of 32)
-    p->blk_ok = p->fuse_ok && J == 16;
-    auto v4ok = [](const GL& g) { return g.split.w && (g.K1 + g.K2) % 32 == 0; };
-    if (!v4ok(p->init_lin) || !v4ok(p->fres_res) || !v4ok(p->fglin)) p->blk_ok = false;
-    for (auto& g : p->r1)
-        if (!v4ok(g)) p->blk_ok = false;
-    for (auto& g : p->r2)
-        if (!v4ok(g)) p->blk_ok = false;
-    for (size_t l = 0; l < p->outp.size(); ++l)
-        if (p->has_attn[l] && !v4ok(p->outp[l])) p->blk_ok = false;
+    p->blk_ok = p->fuse_ok && J == 16 && all_gl_v4(p, &GL::split);
 
     // time MLP (generator.py:50-55, 97) and per-block FiLM tables (attention.py:81-84, 96-100)
     float *emb = nullptr, *t1 = nullptr, *temb = nullptr;
@@ -871,7 +887,7 @@ int sd_plan_finalize(sd_plan* p, void* stream_) {
 
 size_t sd_workspace_bytes(const sd_plan* plan, int64_t rows) {
     if (!plan || rows < 0) return 0;
-    return carve(plan, rows, nullptr, nullptr) + 256;
+    return sd::ws_carve(plan->ws_dims(), rows).bytes + 256;  // + 256: the caller's pointer is aligned up
 }
 
 int32_t sd_plan_kernels_per_step(const sd_plan* p) {
@@ -885,11 +901,11 @@ int32_t sd_plan_kernels_per_step(const sd_plan* p) {
 static int ws_setup(const sd_plan* p, int64_t rows, void* ws, size_t bytes, WS* w) {
     if (!p || !p->finalized) return fail(SD_E_STATE, "plan is not finalized");
     if (rows < 0) return fail(SD_E_INVALID, "rows < 0");
-    const size_t need = carve(p, rows, nullptr, nullptr);
+    const size_t need = sd::ws_carve(p->ws_dims(), rows).bytes;
     if (!ws || bytes < need) return fail(SD_E_INVALID, "workspace too small: need " + std::to_string(need));
     char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
     if ((size_t)(base - (char*)ws) + need > bytes) return fail(SD_E_INVALID, "workspace too small after alignment");
-    carve(p, rows, base, w);
+    *w = ws_carve_view(p, rows, base);
     return SD_OK;
 }
 
@@ -904,7 +920,7 @@ int sd_denoiser_forward(const sd_plan* p, const float* x_t, const float* x_cond,
     if (p->C > 0 && !x_cond) return fail(SD_E_INVALID, "x_cond is required (diffusion_conditioning)");
     if (cond_repeat < 1) return fail(SD_E_INVALID, "cond_repeat must be >= 1");
     if ((rc = ws_reset(w, (hipStream_t)stream))) return rc;
-    return run_denoiser(p, x_t, x_cond, cond_repeat, t, x0_out, rows, w, (hipStream_t)stream);
+    return run_denoiser(Call{p, w, rows, (hipStream_t)stream}, x_t, x_cond, cond_repeat, t, x0_out);
 }
 
 int sd_workspace_status(const sd_plan* p, const void* workspace, size_t ws_bytes, uint32_t* flags, void* stream) {
@@ -933,7 +949,9 @@ int sd_denoiser_trace(const sd_plan* p, const float* x_t, const float* x_cond, i
     if (p->C > 0 && !x_cond) return fail(SD_E_INVALID, "x_cond is required (diffusion_conditioning)");
     if (cond_repeat < 1) return fail(SD_E_INVALID, "cond_repeat must be >= 1");
     if ((rc = ws_reset(w, (hipStream_t)stream))) return rc;
-    return run_denoiser(p, x_t, x_cond, cond_repeat, t, x0_out, rows, w, (hipStream_t)stream, nullptr, 0, 0, acts);
+    Call c{p, w, rows, (hipStream_t)stream};
+    c.trace = acts;
+    return run_denoiser(c, x_t, x_cond, cond_repeat, t, x0_out);
 }
 
 int sd_p_sample_update(const sd_plan* p, const float* x0_raw, const float* x_t, const float* eps,
@@ -946,89 +964,37 @@ int sd_p_sample_update(const sd_plan* p, const float* x0_raw, const float* x_t, 
     if (!x0_raw || !x_t || !x_prev) return fail(SD_E_INVALID, "null tensor");
     if (!eps && p->D % 4) return fail(SD_E_INVALID, "device noise needs latent_dim % 4 == 0");
     const int64_t JD = (int64_t)p->J * p->D;
-    return run_update(p, x0_raw, x_t, eps, eps ? eps_rs : JD, eps ? 1 : 2, seed, row0, nullptr, t,
-                      x_prev, nullptr, 0, mean_out, mean_out ? mean_rs : JD, noise_out,
-                      noise_out ? noise_rs : JD, rows, (hipStream_t)stream, nullptr, 0, 0, 0, 0,
-                      !(flags & SD_FLAG_NO_CLIP));
+    sd::UpdArgs u{};
+    u.x0 = x0_raw;
+    u.xt = x_t;
+    u.out = x_prev;
+    u.clip = !(flags & SD_FLAG_NO_CLIP);
+    u.mean_out = mean_out;
+    u.mean_rs = mean_out ? mean_rs : JD;
+    u.noise_out = noise_out;
+    u.noise_rs = noise_out ? noise_rs : JD;
+    u.eps = eps;
+    u.eps_rs = eps ? eps_rs : JD;
+    u.seed = seed;
+    u.row0 = row0;
+    return run_update(Call{p, WS{}, rows, (hipStream_t)stream}, t, u);
 }
 
-static WS shift_ws(const sd_plan* p, const WS& w, int64_t r0, int chain) {
-    WS o = w;
-    const int64_t J = p->J;
-    o.x += r0 * J * p->H;
-    o.r += r0 * J * p->H;
-    o.h += r0 * J * p->H;
-    o.res += r0 * J * p->H;
-    o.qkv += r0 * J * (p->d.use_attention ? 3 * p->hid : p->H);
-    o.o += r0 * J * (p->d.use_attention ? p->hid : p->H);
-    o.x0 += r0 * J * p->D;
-    o.img0 += r0 * J * p->D;
-    o.img1 += r0 * J * p->D;
-    return o;
-}
-
-// number of row chains for `rows` rows (multiples of 32 rows each; the plan's row_chains option,
-// default 3).  Every route runs with any chain count: the kernels share CUs with each other's
-// workgroups (the row-chain hazard of rounds 1-2 was packed-FP32 code, which the
-// build no longer emits), and the results are bitwise independent of the chain count.
-static int chain_count(const sd_plan* p, int64_t rows, int64_t cond_repeat, int64_t* unit) {
-    (void)cond_repeat;  // a chain starting inside a sequence's futures reads x_cond via x1_row0
-    const int64_t g = 32;
-    *unit = g;
-    // a partial last unit counts: 50 rows (config 4, one sequence) run as chains of 32 + 18 rows
-    const int64_t units = (rows + g - 1) / g;
-    // auto (0): 3 chains (+ the caller's stream = HIP's default 4 hardware queues; a 4th chain
-    // shares a queue: config 2 11.9k vs 15.9k futures/s), 2 on the small-batch split route
-    // (400 rows: 5,920 vs 5,398 on one, 3,279 on three), one at 128 rows and below, where every
-    // kernel is a few microseconds long and a second chain slows both (config 4, 50 rows: 61 vs
-    // 106 futures/s; tools/sweep_routes.py, profiles/r03/ab)
-    int n = p->chains > 0 ? std::min(p->chains, (int)sd_plan::kMaxChains)
-            : rows <= 128            ? 1
-            : rows <= sd::kSplitRows ? 2
-                                     : 3;
-    if (units < n) n = (int)std::max<int64_t>(1, units);
-    return n;
-}
-static int64_t chain_row(int i, int n, int64_t rows, int64_t unit) {
-    return i >= n ? rows : std::min(rows, (rows + unit - 1) / unit * i / n * unit);
-}
-
-// Chain boundaries on the tiled route's GEMM tile.  k_gl4t's workgroup covers 256
-// rows at RT = 2 (N <= 192) and 128 at RT = 1 (to_qkv), and a tile past the chain's rows still
-// loads and multiplies (gl4t_body skips its stores only): cut on 32-row units, 3,200 rows on three
-// chains are 33 / 33 / 34 tiles, 15 row groups of 256 where 12.5 hold data.  On kChainTileUnit
-// rows the cuts leave whole waves / workgroups to all chains but the last.  Only where every chain
-// keeps two full 256-row workgroups; below that the 32-row cuts stay (so do the small batches'
-// chain shapes).  Rows are independent and the Philox rows / x_cond phase follow r0, so the
-// results do not depend on where the cuts fall.
-constexpr int64_t kChainTileUnit = 128;
-static_assert(kChainTileUnit >= 32 && kChainTileUnit % 32 == 0, "chains start on 32-row blocks");
-static int64_t chain_start(int64_t rows, int n, int64_t unit, int i) {
-    if (n < 1) n = 1;
-    if (unit > 32) {
-        if (unit % 32) unit = 32;
-        for (int k = 0; k < n && unit > 32; ++k)
-            if (chain_row(k + 1, n, rows, unit) - chain_row(k, n, rows, unit) < 512) unit = 32;
-    } else {
-        unit = 32;
-    }
-    return chain_row(i, n, rows, unit);
-}
 // whether the graph-linears of a sampling call over `rows` rows take the tiled split route
 // (k_gl4t): the route of a ResnetBlock layer as run_denoiser sets it up (the route follows the
 // whole call's rows, GLArgs::route_rows, not a chain's)
 static bool tiled_route_call(const sd_plan* p, int64_t rows, const WS& w) {
     if (!p->blocked_now() || p->r1.empty()) return false;
-    sd::GLArgs a = gl_args(p, p->r1[0], w.r, 1, nullptr, nullptr, nullptr, w.h, rows);
+    sd::GLArgs a = gl_args(p, p->r1[0], w.r, w.h, rows);
     a.zs = w.qkv;
-    a.zs_cap = (rows + 31) / 32 * 32 * p->J * qkv_width(p);
+    a.zs_cap = w.zs_cap;
     a.route_rows = rows;
     return sd::graph_linear_split_route(a) == 2;
 }
 int64_t sd_chain_start(int64_t rows, int32_t nchains, int64_t unit, int32_t i) {
-    return rows <= 0 || i <= 0 ? 0 : chain_start(rows, nchains, unit, i);
+    return rows <= 0 || i <= 0 ? 0 : sd::chain_start(rows, nchains, unit, i);
 }
-int64_t sd_chain_tile_unit(void) { return kChainTileUnit; }
+int64_t sd_chain_tile_unit(void) { return sd::kChainTileUnit; }
 
 // Creates the auxiliary streams / fork-join events chains 1 .. n-1 use (caller holds cmu).
 static int ensure_chains(sd_plan* mp, int n) {
@@ -1044,56 +1010,83 @@ static int ensure_chains(sd_plan* mp, int n) {
 // records every row chain (chain i on cs[i]; steps outer, chains inner, so an eager caller feeds
 // every chain from the start); only = i records chain i alone on cs[i] (one captured graph per
 // chain, see sd_sample_loop).
-static int record_loop(const sd_plan* p, const float* x_T, const float* x_cond, int64_t cond_repeat,
-                       const float* eps_all, uint64_t seed, int64_t row0, float* out, float* means,
-                       float* noise_out, float* timages, float* start_out, int64_t rows, const WS& w,
-                       int32_t flags, bool use_rng_dev, const hipStream_t* cs, int nch, int64_t unit, int only) {
+struct LoopArgs {  // sd_sample_loop's tensors and scalars, under its parameter names
+    const float *x_T, *x_cond;
+    int64_t cond_repeat;
+    const float* eps_all;
+    uint64_t seed;
+    int64_t row0;
+    float *out, *means, *noise_out, *timages, *start_out;
+    int64_t rows;
+    int32_t flags;
+};
+struct ChainSet {  // the row chains of one call: their streams, and the unit their cuts fall on
+    hipStream_t cs[sd_plan::kMaxChains];
+    int n;
+    int64_t unit;
+};
+static int record_loop(const sd_plan* p, const LoopArgs& a, const WS& w, const ChainSet& chains, bool use_rng_dev,
+                       int only) {
     const int T = p->T;
     const int64_t JD = (int64_t)p->J * p->D;
     const int64_t step_rs = (int64_t)(T > 1 ? T - 1 : 1) * JD;  // row stride of (B, T-1, J, D)
     const uint64_t* rng = use_rng_dev ? w.rng : nullptr;
-    const bool dev_start = (flags & SD_FLAG_DEVICE_START) != 0;
-    const bool dev_noise = (flags & SD_FLAG_DEVICE_NOISE) != 0;
+    const bool dev_start = (a.flags & SD_FLAG_DEVICE_START) != 0;
+    const bool dev_noise = (a.flags & SD_FLAG_DEVICE_NOISE) != 0;
     const int bf = p->prec == 2;  // bf16 latents (x_t, x0 between steps); records and `out` f32
+    const int nch = chains.n;
     struct Chain {
-        int64_t r0, n;
-        WS w;
+        int64_t r0;
+        Call call;
         const float* cur;
     } ch[sd_plan::kMaxChains];
     const int c0 = only < 0 ? 0 : only, c1 = only < 0 ? nch : only + 1;
     for (int i = c0; i < c1; ++i) {
-        Chain& c = ch[i];
-        c.r0 = chain_start(rows, nch, unit, i);
-        c.n = chain_start(rows, nch, unit, i + 1) - c.r0;
-        c.w = shift_ws(p, w, c.r0, i);
-        c.cur = (dev_start || bf) ? c.w.img1 : x_T + c.r0 * JD;
-        if (dev_start) SD_HIP(sd::launch_noise_fill(c.w.img1, c.n, JD, seed, row0, T, rng, cs[i], c.r0, bf));
+        const int64_t r0 = sd::chain_start(a.rows, nch, chains.unit, i);
+        const int64_t n = sd::chain_start(a.rows, nch, chains.unit, i + 1) - r0;
+        Call call{p, ws_chain_view(p, w, r0, n), n, chains.cs[i]};
+        call.route_rows = a.rows;
+        call.cond_phase = r0 % a.cond_repeat;
+        // concurrent chains: 32 x 64 tiles (more, smaller workgroups to interleave) measured
+        // 5 % faster than the single-chain 32 x 96 choice at B = 3200, 3 chains
+        const int64_t wg813 = (n + 31) / 32 * 2;  // 32 x 96 workgroups of an N = 192 layer
+        call.tile_hint = (nch > 1 && wg813 >= 32) ? 812 : 0;
+        call.lat_bf16 = bf;
+        const WS& cw = call.w;
+        const float* cur = (dev_start || bf) ? cw.img1 : a.x_T + r0 * JD;
+        if (dev_start) SD_HIP(sd::launch_noise_fill(cw.img1, n, JD, a.seed, a.row0, T, rng, call.s, r0, bf));
         else if (bf)  // bf16 latents: the caller's f32 start noise rounded once
-            SD_HIP(sd::launch_convert_rows(c.w.img1, 1, JD, x_T + c.r0 * JD, 0, JD, c.n, JD, cs[i]));
-        if (start_out) SD_HIP(sd::launch_convert_rows(start_out + c.r0 * JD, 0, JD, c.cur, bf, JD, c.n, JD, cs[i]));
+            SD_HIP(sd::launch_convert_rows(cw.img1, 1, JD, a.x_T + r0 * JD, 0, JD, n, JD, call.s));
+        if (a.start_out) SD_HIP(sd::launch_convert_rows(a.start_out + r0 * JD, 0, JD, cur, bf, JD, n, JD, call.s));
+        ch[i] = Chain{r0, call, cur};
     }
     for (int t = T - 1; t >= 0; --t) {
         const int64_t k = T - 1 - t;  // index into the (B, T-1, ...) records
-        const bool rec = t > 0;
         for (int i = c0; i < c1; ++i) {
             Chain& c = ch[i];
-            const int64_t r0 = c.r0;
-            const float* xc = (p->C > 0) ? x_cond + (r0 / cond_repeat) * p->J * p->C : x_cond;
-            // concurrent chains: 32 x 64 tiles (more, smaller workgroups to interleave) measured
-            // 5 % faster than the single-chain 32 x 96 choice at B = 3200, 3 chains
-            const int64_t wg813 = (c.n + 31) / 32 * 2;  // 32 x 96 workgroups of an N = 192 layer
-            int rc = run_denoiser(p, c.cur, xc, cond_repeat, t, c.w.x0, c.n, c.w, cs[i], nullptr, r0 % cond_repeat,
-                                  (nch > 1 && wg813 >= 32) ? 812 : 0, nullptr, bf, bf, rows);
+            const WS& cw = c.call.w;
+            const int64_t r0 = c.r0, roff = r0 * step_rs + k * JD;  // this chain's rows of step k's records
+            const float* xc = (p->C > 0) ? a.x_cond + (r0 / a.cond_repeat) * p->J * p->C : a.x_cond;
+            int rc = run_denoiser(c.call, c.cur, xc, a.cond_repeat, t, cw.x0);
             if (rc) return rc;
-            float* nxt = (t == 0) ? out + r0 * JD : (((T - 1 - t) & 1) ? c.w.img1 : c.w.img0);
-            const float* eps = (!dev_noise && t > 0) ? eps_all + r0 * step_rs + k * JD : nullptr;
-            rc = run_update(p, c.w.x0, c.cur, eps, step_rs, dev_noise ? 2 : 1, seed, row0, rng, t, nxt,
-                            (rec && timages) ? timages + r0 * step_rs + k * JD : nullptr, step_rs,
-                            (rec && means) ? means + r0 * step_rs + k * JD : nullptr, step_rs,
-                            (rec && noise_out) ? noise_out + r0 * step_rs + k * JD : nullptr, step_rs, c.n,
-                            cs[i], nullptr, r0, bf, bf, t > 0 ? bf : 0, !(flags & SD_FLAG_NO_CLIP));
-            if (rc) return rc;
-            c.cur = nxt;
+            auto rec = [&](float* q) { return (t > 0 && q) ? q + roff : nullptr; };
+            sd::UpdArgs u{};
+            u.x0 = cw.x0;
+            u.xt = c.cur;
+            u.out = (t == 0) ? a.out + r0 * JD : ((k & 1) ? cw.img1 : cw.img0);
+            u.out_bf16 = t > 0 ? bf : 0;
+            u.clip = !(a.flags & SD_FLAG_NO_CLIP);
+            u.out2 = rec(a.timages);
+            u.mean_out = rec(a.means);
+            u.noise_out = rec(a.noise_out);
+            u.out2_rs = u.mean_rs = u.noise_rs = u.eps_rs = step_rs;
+            u.eps = (!dev_noise && t > 0) ? a.eps_all + roff : nullptr;
+            u.seed = a.seed;
+            u.row0 = a.row0;
+            u.rng_dev = rng;
+            u.row_shift = r0;
+            if ((rc = run_update(c.call, t, u))) return rc;
+            c.cur = u.out;
         }
     }
     return SD_OK;
@@ -1136,12 +1129,14 @@ int sd_sample_loop(const sd_plan* p, const float* x_T, const float* x_cond, int6
     hipStream_t s = (hipStream_t)stream;
     sd_plan* mp = const_cast<sd_plan*>(p);
     if ((rc = ws_reset(w, s))) return rc;
-    int64_t unit = 32;
-    const int nch = chain_count(p, rows, cond_repeat, &unit);
-    if (nch > 1 && tiled_route_call(p, rows, w)) unit = kChainTileUnit;  // chain_start: where every chain keeps 512 rows
+    // a chain starting inside a sequence's futures reads x_cond via x1_row0: the count ignores cond_repeat
+    const int nch = sd::chain_count(p->chains, rows, sd::kSplitRows);
+    const LoopArgs la{x_T, x_cond, cond_repeat, eps_all, seed, row0, out, means_out, noise_out, timages_out, start_out, rows, flags};
+    ChainSet chains{{}, nch, 32};
+    if (nch > 1 && tiled_route_call(p, rows, w)) chains.unit = sd::kChainTileUnit;  // chain_start: where every chain keeps 512 rows
     mp->last_chains.store(nch);
     std::unique_lock<std::mutex> lk(mp->cmu, std::defer_lock);  // fork/join objects are shared
-    hipStream_t cs[sd_plan::kMaxChains];
+    hipStream_t* cs = chains.cs;
     cs[0] = s;
     if (nch > 1) {
         lk.lock();
@@ -1151,8 +1146,7 @@ int sd_sample_loop(const sd_plan* p, const float* x_T, const float* x_cond, int6
     if (!(flags & SD_FLAG_GRAPH)) {
         if ((rc = fork_chains(mp, s, nch, cs))) return rc;
         sd::g_route_bits = 0;
-        rc = record_loop(p, x_T, x_cond, cond_repeat, eps_all, seed, row0, out, means_out, noise_out, timages_out,
-                         start_out, rows, w, flags, false, cs, nch, unit, -1);
+        rc = record_loop(p, la, w, chains, false, -1);
         mp->last_route.store(sd::g_route_bits);
         if (rc) return rc;
         return join_chains(mp, s, nch, cs);
@@ -1171,13 +1165,7 @@ int sd_sample_loop(const sd_plan* p, const float* x_T, const float* x_cond, int6
     key.flags = flags;
     key.chains = nch;
     key.prec = p->prec;
-    key.variant = p->variant;
-    key.gl4_cfg = p->gl4_cfg;
-    key.gl4_stage = p->gl4_stage;
-    key.split = p->split;
-    key.upd_elem = p->upd_elem;
-    key.v5_valu = p->v5_valu;
-    key.attn_tail = p->attn_tail;
+    key.opts = p->opts;
     key.stream = stream;
     SD_HIP(sd::launch_set_rng(w.rng, seed, row0, s));
     std::shared_ptr<GraphSet> set;
@@ -1195,8 +1183,7 @@ int sd_sample_loop(const sd_plan* p, const float* x_T, const float* x_cond, int6
             hipGraphExec_t exec = nullptr;
             hipError_t e = hipStreamBeginCapture(cs[i], hipStreamCaptureModeThreadLocal);
             if (e == hipSuccess) {
-                rc = record_loop(p, x_T, x_cond, cond_repeat, eps_all, seed, row0, out, means_out, noise_out,
-                                 timages_out, start_out, rows, w, flags, true, cs, nch, unit, i);
+                rc = record_loop(p, la, w, chains, true, i);
                 e = hipStreamEndCapture(cs[i], &graph);
                 if (!rc && e == hipSuccess) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
                 if (graph) (void)hipGraphDestroy(graph);
@@ -1266,11 +1253,16 @@ int sd_profile_step(const sd_plan* p, const float* x_t, const float* x_cond, int
     int32_t counts[3] = {0, 0, 0};
     for (int r = 0; r < reps; ++r) {
         Prof prof;
-        rc = run_denoiser(p, x_t, x_cond, cond_repeat, t, w.x0, rows, w, s, &prof);
-        if (rc) return rc;
-        rc = run_update(p, w.x0, x_t, nullptr, 0, 2, 1234 + r, 0, nullptr, t, w.img0, nullptr, 0, nullptr, 0,
-                        nullptr, 0, rows, s, &prof);
-        if (rc) return rc;
+        Call c{p, w, rows, s};
+        c.prof = &prof;
+        if ((rc = run_denoiser(c, x_t, x_cond, cond_repeat, t, w.x0))) return rc;
+        sd::UpdArgs u{};  // no eps: Philox noise
+        u.x0 = w.x0;
+        u.xt = x_t;
+        u.out = w.img0;
+        u.clip = 1;
+        u.seed = 1234 + r;
+        if ((rc = run_update(c, t, u))) return rc;
         SD_HIP(hipStreamSynchronize(s));
         for (size_t i = 0; i < prof.cls.size(); ++i) {
             float ms = 0.f;
@@ -1285,89 +1277,6 @@ int sd_profile_step(const sd_plan* p, const float* x_t, const float* x_cond, int
     for (int i = 0; i < 4; ++i) ms_out[i] = (float)(acc[i] / reps);
     if (counts_out)
         for (int i = 0; i < 3; ++i) counts_out[i] = counts[i];
-    return SD_OK;
-}
-
-int sd_pairwise_distances(const float* x, int64_t nseq, int32_t samples, int64_t features, float* l1_mean,
-                          float* l2_mean, void* stream) {
-    if (nseq < 0 || samples < 2 || samples > 64 || features < 1)
-        return fail(SD_E_INVALID, "pairwise distances: need 2..64 samples, features >= 1");
-    if (nseq == 0) return SD_OK;
-    if (!x) return fail(SD_E_INVALID, "pairwise distances: null input");
-    SD_HIP(sd::launch_pairwise(x, nseq, samples, features, l1_mean, l2_mean, (hipStream_t)stream));
-    return SD_OK;
-}
-
-int sd_ade_fde(const float* pred, const float* target, int64_t nseq, int32_t samples, int32_t frames,
-               int64_t features, float* ade, float* fde, float* per_sample_ade, float* per_sample_fde, void* stream) {
-    if (nseq < 0 || samples < 1 || samples > 64 || frames < 1 || features < 1)
-        return fail(SD_E_INVALID, "ade/fde: need 1..64 samples, frames >= 1, features >= 1");
-    if (nseq == 0) return SD_OK;
-    if (!pred || !target) return fail(SD_E_INVALID, "ade/fde: null input");
-    SD_HIP(sd::launch_ade_fde(pred, target, nseq, samples, frames, features, ade, fde, per_sample_ade, per_sample_fde,
-                              (hipStream_t)stream));
-    return SD_OK;
-}
-
-int sd_mm_ade_fde(const float* pred, const float* gts, const int64_t* pair_seq, int64_t npairs,
-                  const int64_t* seq_offsets, int64_t nseq, int32_t samples, int32_t frames, int64_t features,
-                  float* pair_ade, float* pair_fde, float* mmade, float* mmfde, void* stream) {
-    if (nseq < 0 || npairs < 0 || samples < 1 || samples > 64 || frames < 1 || features < 1)
-        return fail(SD_E_INVALID, "mmade/mmfde: need 1..64 samples, frames >= 1, features >= 1");
-    if (nseq == 0) return SD_OK;
-    if (!seq_offsets || (npairs > 0 && (!pred || !gts || !pair_seq)) || (mmade && !pair_ade) || (mmfde && !pair_fde))
-        return fail(SD_E_INVALID, "mmade/mmfde: null input (pair outputs are required for the means)");
-    SD_HIP(sd::launch_mm_ade_fde(pred, gts, pair_seq, npairs, seq_offsets, nseq, samples, frames, features, pair_ade,
-                                 pair_fde, mmade, mmfde, (hipStream_t)stream));
-    return SD_OK;
-}
-
-int sd_best_of_k(const float* sim, const float* loss, int64_t nseq, int32_t k, int64_t* idx_out, float* loss_out,
-                 void* stream) {
-    if (nseq < 0 || k < 1) return fail(SD_E_INVALID, "best_of_k: nseq >= 0, k >= 1");
-    if (nseq == 0) return SD_OK;
-    if (!loss || (!idx_out && !loss_out)) return fail(SD_E_INVALID, "best_of_k: null buffer");
-    SD_HIP(sd::launch_best_of_k(sim, loss, nseq, k, idx_out, loss_out, (hipStream_t)stream));
-    return SD_OK;
-}
-
-int sd_best_of_k_backward(const float* dloss_sel, const int64_t* idx, int64_t nseq, int32_t k, float* dloss,
-                          void* stream) {
-    if (nseq < 0 || k < 1) return fail(SD_E_INVALID, "best_of_k_backward: nseq >= 0, k >= 1");
-    if (nseq == 0) return SD_OK;
-    if (!dloss_sel || !idx || !dloss) return fail(SD_E_INVALID, "best_of_k_backward: null buffer");
-    SD_HIP(sd::launch_best_of_k_bwd(dloss_sel, idx, nseq, k, dloss, (hipStream_t)stream));
-    return SD_OK;
-}
-
-int sd_pose_loss(const float* pred, const float* target, int64_t nseq, int32_t samples, int32_t frames,
-                 int32_t joints, int32_t dims, int32_t mse, float* per_sample, void* stream) {
-    if (nseq < 0 || samples < 1 || frames < 1 || joints < 1 || dims < 1)
-        return fail(SD_E_INVALID, "pose_loss: samples, frames, joints, dims >= 1");
-    if (nseq == 0) return SD_OK;
-    if (!pred || !target || !per_sample) return fail(SD_E_INVALID, "pose_loss: null buffer");
-    SD_HIP(sd::launch_pose_loss(pred, target, nseq, samples, frames, joints, dims, mse != 0, per_sample,
-                                (hipStream_t)stream));
-    return SD_OK;
-}
-
-int sd_best_sample(const float* pred, const float* target, int64_t nseq, int32_t samples, int32_t frames,
-                   int32_t joints, int32_t coords, int32_t tail_frames, float* per_sample, float* min_out,
-                   int64_t* idx_out, float* best_out, float* tail_out, void* stream) {
-    if (nseq < 0 || nseq > INT32_MAX) return fail(SD_E_INVALID, "best_sample: nseq must be in 0..2^31-1");
-    if (samples < 1 || samples > 64) return fail(SD_E_INVALID, "best_sample: samples must be in 1..64");
-    if (coords != 3) return fail(SD_E_INVALID, "best_sample: coords must be 3");
-    if (frames < 1) return fail(SD_E_INVALID, "best_sample: frames must be >= 1");
-    if (joints < 1) return fail(SD_E_INVALID, "best_sample: joints must be >= 1");
-    if (tail_frames < 0 || tail_frames > frames)
-        return fail(SD_E_INVALID, "best_sample: tail_frames must be in 0..frames");
-    if (tail_out && tail_frames == 0) return fail(SD_E_INVALID, "best_sample: tail_out given with tail_frames = 0");
-    if (nseq == 0) return SD_OK;
-    if (!pred) return fail(SD_E_INVALID, "best_sample: pred is null");
-    if (!target) return fail(SD_E_INVALID, "best_sample: target is null");
-    if (!per_sample) return fail(SD_E_INVALID, "best_sample: per_sample is required (it is the workspace)");
-    SD_HIP(sd::launch_best_sample(pred, target, nseq, samples, frames, joints, tail_frames, per_sample, min_out, idx_out,
-                                  best_out, tail_out, (hipStream_t)stream));
     return SD_OK;
 }
 
@@ -1403,11 +1312,11 @@ int sd_plan_set_option(sd_plan* p, int32_t option, int64_t value) {
                 return fail(SD_E_INVALID, "bf16 mode runs on the v4 kernels only (variant 0 or 4)");
             if (p->d.norm_type == 1 && value != 0 && value != 4)
                 return fail(SD_E_INVALID, "norm_type 'layer' runs on the v4 kernels only (variant 0 or 4)");
-            p->variant = (int)value;
+            p->opts.variant = (int)value;
             return SD_OK;
         case SD_OPT_GL4_TILE:
             if (value < 0) return fail(SD_E_INVALID, "gl4 tile must be >= 0");
-            p->gl4_cfg = (int)value;
+            p->opts.gl4_cfg = (int)value;
             return SD_OK;
         case SD_OPT_ROW_CHAINS:
             if (value < 0 || value > sd_plan::kMaxChains) return fail(SD_E_INVALID, "row chains must be in [0 (auto), 8]");
@@ -1417,7 +1326,7 @@ int sd_plan_set_option(sd_plan* p, int32_t option, int64_t value) {
         case SD_OPT_GL4_STAGING:
             if (value < 0 || value > 2)
                 return fail(SD_E_INVALID, "gl4 staging must be 0 (LDS-DMA), 1 (registers) or 2 (diagnostic)");
-            p->gl4_stage = (int)value;
+            p->opts.gl4_stage = (int)value;
             return SD_OK;
         case SD_OPT_LAST_CHAINS:
         case SD_OPT_LAST_ROUTE: return fail(SD_E_INVALID, "SD_OPT_LAST_CHAINS / SD_OPT_LAST_ROUTE are read-only");
@@ -1425,22 +1334,22 @@ int sd_plan_set_option(sd_plan* p, int32_t option, int64_t value) {
             if (value < 0 || value > 4)
                 return fail(SD_E_INVALID, "split route must be 0 (auto), 1 (never), 2 (always), 3 (always, tiled phase 1) "
                                           "or 4 (tiled phase 1 except to_qkv + attention)");
-            p->split = (int)value;
+            p->opts.split = (int)value;
             return SD_OK;
         case SD_OPT_UPDATE_KERNEL:
             if (value < 0 || value > 1)
                 return fail(SD_E_INVALID, "update kernel must be 0 (matrix cores where they apply) or 1 (element-per-thread)");
-            p->upd_elem = (int)value;
+            p->opts.upd_elem = (int)value;
             return SD_OK;
         case SD_OPT_V5_MIX:
             if (value != 0 && value != 1) return fail(SD_E_INVALID, "v5 mix must be 0 (matrix cores) or 1 (VALU)");
-            p->v5_valu = (int)value;
+            p->opts.v5_valu = (int)value;
             return SD_OK;
         case SD_OPT_ATTENTION:
             if (value != 0 && value != 2 && value != 3)
                 return fail(SD_E_INVALID, "attention must be 0 (auto: 2 where it applies), 2 (to_qkv mixing inside the "
                                           "attention kernel at 49 <= J <= 52) or 3 (the separate mixing pass)");
-            p->attn_tail = (int)value;
+            p->opts.attn_tail = (int)value;
             return SD_OK;
         default: return fail(SD_E_INVALID, "unknown option " + std::to_string(option));
     }
@@ -1449,17 +1358,17 @@ int sd_plan_set_option(sd_plan* p, int32_t option, int64_t value) {
 int sd_plan_get_option(const sd_plan* p, int32_t option, int64_t* value) {
     if (!p || !value) return fail(SD_E_INVALID, "null argument");
     switch (option) {
-        case SD_OPT_KERNEL_VARIANT: *value = p->variant; return SD_OK;
-        case SD_OPT_GL4_TILE: *value = p->gl4_cfg; return SD_OK;
+        case SD_OPT_KERNEL_VARIANT: *value = p->opts.variant; return SD_OK;
+        case SD_OPT_GL4_TILE: *value = p->opts.gl4_cfg; return SD_OK;
         case SD_OPT_ROW_CHAINS: *value = p->chains; return SD_OK;
         case SD_OPT_PRECISION: *value = p->prec; return SD_OK;
-        case SD_OPT_GL4_STAGING: *value = p->gl4_stage; return SD_OK;
-        case SD_OPT_SPLIT_ROUTE: *value = p->split; return SD_OK;
+        case SD_OPT_GL4_STAGING: *value = p->opts.gl4_stage; return SD_OK;
+        case SD_OPT_SPLIT_ROUTE: *value = p->opts.split; return SD_OK;
         case SD_OPT_LAST_CHAINS: *value = p->last_chains.load(); return SD_OK;
         case SD_OPT_LAST_ROUTE: *value = p->last_route.load(); return SD_OK;
-        case SD_OPT_UPDATE_KERNEL: *value = p->upd_elem; return SD_OK;
-        case SD_OPT_V5_MIX: *value = p->v5_valu; return SD_OK;
-        case SD_OPT_ATTENTION: *value = p->attn_tail; return SD_OK;
+        case SD_OPT_UPDATE_KERNEL: *value = p->opts.upd_elem; return SD_OK;
+        case SD_OPT_V5_MIX: *value = p->opts.v5_valu; return SD_OK;
+        case SD_OPT_ATTENTION: *value = p->opts.attn_tail; return SD_OK;
         default: return fail(SD_E_INVALID, "unknown option " + std::to_string(option));
     }
 }
@@ -1470,16 +1379,9 @@ int sd_plan_set_precision(sd_plan* p, int32_t mode) {
     if (mode == 2) {  // the bf16 operands exist only in the v4 tiles (J 16 / 17 / 21, row-major)
         if (p->J != 16 && p->J != 17 && p->J != 21)
             return fail(SD_E_INVALID, "bf16 mode needs the split-f16 (v4) tiles: num_nodes 16, 17 or 21");
-        if (p->variant != 0 && p->variant != 4) return fail(SD_E_INVALID, "bf16 mode needs kernel variant 0 or 4");
-        if (p->finalized) {
-            auto v4ok = [](const GL& g) { return g.split_bf.w && (g.K1 + g.K2) % 32 == 0; };
-            bool ok = v4ok(p->init_lin) && v4ok(p->fres_res) && v4ok(p->fglin);
-            for (auto& g : p->r1) ok = ok && v4ok(g);
-            for (auto& g : p->r2) ok = ok && v4ok(g);
-            for (size_t l = 0; l < p->qkv.size(); ++l)
-                if (p->has_attn[l]) ok = ok && v4ok(p->qkv[l]) && (!p->d.use_attention || v4ok(p->outp[l]));
-            if (!ok) return fail(SD_E_INVALID, "bf16 mode needs every graph-linear on the v4 kernels (K % 32 == 0)");
-        }
+        if (p->opts.variant != 0 && p->opts.variant != 4) return fail(SD_E_INVALID, "bf16 mode needs kernel variant 0 or 4");
+        if (p->finalized && !all_gl_v4(p, &GL::split_bf))
+            return fail(SD_E_INVALID, "bf16 mode needs every graph-linear on the v4 kernels (K % 32 == 0)");
     }
     p->prec = mode;
     return SD_OK;
@@ -1500,33 +1402,17 @@ int sd_test_graph_linear_layout(const float* x1, int32_t K1, int64_t x1_div, con
     if (!x1 || !W || !ghat || !out || !node_types || J < 1 || J > sd::kMaxNodes || N < 1 || K1 % 16 ||
         K2 % 16 || x1_div < 1 || rows < 0)
         return fail(SD_E_INVALID, "bad arguments");
-    sd::GLArgs a{};
-    a.x1 = x1;
-    a.K1 = K1;
-    a.x1_rs = (int64_t)J * K1;
+    if (std::any_of(node_types, node_types + J, [](int64_t v) { return v < 0; })) return fail(SD_E_INVALID, "negative node type");
+    sd::GLArgs a = gl_build(GLShape{J, K1, K2, N}, x1, out, rows, node_types, 0);
     a.x1_div = (int)x1_div;
     a.x2 = x2;
-    a.K2 = x2 ? K2 : 0;
-    a.x2_rs = (int64_t)J * K2;
+    if (!x2) a.K2 = 0;
     a.W = W;
     a.bias = bias;
     a.G = ghat;
     a.film = film;
     a.res = res;
-    a.res_rs = (int64_t)J * N;
-    a.out = out;
-    a.out_rs = (int64_t)J * N;
-    a.B = rows;
-    a.N = N;
-    a.J = J;
     a.act = act;
-    a.ntypes = 1;
-    for (int j = 0; j < J; ++j) {
-        if (node_types[j] < 0) return fail(SD_E_INVALID, "negative node type");
-        a.wrow[j] = (int)node_types[j] * N;
-        a.ntype[j] = (int)node_types[j];
-        a.ntypes = std::max(a.ntypes, (int)node_types[j] + 1);
-    }
     a.x1_blk = layout & 1;
     a.x2_blk = (layout >> 1) & 1;
     a.res_blk = (layout >> 2) & 1;
@@ -1536,9 +1422,7 @@ int sd_test_graph_linear_layout(const float* x1, int32_t K1, int64_t x1_div, con
     sd::SplitW sw;  // split weights for v4, made and freed per call
     if (a.variant == 0 || a.variant == 4) {
         SD_HIP(sd::make_split_weights(W, a.ntypes, N, K1 + a.K2, &sw, (hipStream_t)stream));
-        a.wsp = sw.w;
-        a.wsp_nct = sw.nct;
-        a.wsp_unscale = sw.unscale;
+        gl_set_split(a, sw);
     }
     a.split = g_test_split;
     float* zs = nullptr;
@@ -1562,25 +1446,11 @@ int sd_test_qkv_attention(const float* x, int32_t K, const float* W, const int64
                           void* stream) {
     if (!x || !W || !ghat || !out || !node_types || J < 1 || J > sd::kMaxNodes || heads < 1 || K % 32 || rows < 0)
         return fail(SD_E_INVALID, "bad arguments");
-    sd::GLArgs a{};
+    if (std::any_of(node_types, node_types + J, [](int64_t v) { return v < 0; })) return fail(SD_E_INVALID, "negative node type");
     const int N = 3 * heads * 32;
-    a.x1 = x;
-    a.K1 = K;
-    a.x1_rs = (int64_t)J * K;
-    a.x1_div = 1;
+    sd::GLArgs a = gl_build(GLShape{J, K, 0, N}, x, out, rows, node_types, 0);
     a.G = ghat;
-    a.out = out;
     a.out_rs = (int64_t)J * heads * 32;
-    a.B = rows;
-    a.N = N;
-    a.J = J;
-    a.ntypes = 1;
-    for (int j = 0; j < J; ++j) {
-        if (node_types[j] < 0) return fail(SD_E_INVALID, "negative node type");
-        a.wrow[j] = (int)node_types[j] * N;
-        a.ntype[j] = (int)node_types[j];
-        a.ntypes = std::max(a.ntypes, (int)node_types[j] + 1);
-    }
     a.attn_heads = heads;
     a.attn_scale = (float)std::pow(32.0, -0.5);
     a.variant = g_test_variant;
@@ -1589,9 +1459,7 @@ int sd_test_qkv_attention(const float* x, int32_t K, const float* W, const int64
     a.out_blk = (layout >> 3) & 1;
     sd::SplitW sw;
     SD_HIP(sd::make_split_weights(W, a.ntypes, N, K, &sw, (hipStream_t)stream));
-    a.wsp = sw.w;
-    a.wsp_nct = sw.nct;
-    a.wsp_unscale = sw.unscale;
+    gl_set_split(a, sw);
     const hipError_t e = sd::launch_qkv_attention_v4(a, rms != 0, (hipStream_t)stream);
     (void)hipStreamSynchronize((hipStream_t)stream);
     (void)hipFree(sw.w);

@@ -818,12 +818,6 @@ size_t mahalanobis_lds(int J, int F) { return ((size_t)2 * J * F + (size_t)J * J
 
 using sd::GemmArgs;
 
-#define TR_HIP(x)                                                                                     \
-    do {                                                                                              \
-        hipError_t e_ = (x);                                                                          \
-        if (e_ != hipSuccess) return sd::set_error(SD_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 extern "C" {
 
 size_t sd_gl_train_workspace_bytes(int64_t rows, int32_t J, int32_t K, int32_t N, int32_t n_types) {
@@ -854,8 +848,8 @@ int sd_gl_train_forward(const float* x, const float* W, const float* bias, const
     g.am = (int64_t)J * K; g.ak = 1; g.aj = K; g.at = 0;            // A[m][k] = x[m, j, k]
     g.bk = 1; g.bn = K; g.bj = 0; g.bt = (int64_t)N * K;            // B[k][n] = W[t][n][k]
     g.cm = (int64_t)J * N; g.cz = N; g.cs = 0; g.bias_t = N;        // C[m][n] = z[m, j, n]
-    TR_HIP(sd::launch_gemm(g, dim3((unsigned)sd::ceil_div(N, sd::TN), (unsigned)sd::ceil_div(rows, sd::TM), J), s));
-    TR_HIP(sd::launch_mix(z, ghat, y, rows, J, N, 0, s));
+    SD_HIP(sd::launch_gemm(g, dim3((unsigned)sd::ceil_div(N, sd::TN), (unsigned)sd::ceil_div(rows, sd::TM), J), s));
+    SD_HIP(sd::launch_mix(z, ghat, y, rows, J, N, 0, s));
     return SD_OK;
 }
 
@@ -871,9 +865,9 @@ int sd_gl_train_backward(const float* x, const float* z, const float* dy, const 
     if (n_types > 0 && !node_types) return sd::set_error(SD_E_INVALID, "gl_train_backward: node_types missing");
     hipStream_t s = (hipStream_t)stream;
     if (rows == 0) {  // empty batch: zero parameter gradients
-        if (dW) TR_HIP(hipMemsetAsync(dW, 0, (size_t)types * N * K * sizeof(float), s));
-        if (dbias) TR_HIP(hipMemsetAsync(dbias, 0, (size_t)types * N * sizeof(float), s));
-        if (dghat) TR_HIP(hipMemsetAsync(dghat, 0, (size_t)J * J * sizeof(float), s));
+        if (dW) SD_HIP(hipMemsetAsync(dW, 0, (size_t)types * N * K * sizeof(float), s));
+        if (dbias) SD_HIP(hipMemsetAsync(dbias, 0, (size_t)types * N * sizeof(float), s));
+        if (dghat) SD_HIP(hipMemsetAsync(dghat, 0, (size_t)J * J * sizeof(float), s));
         return SD_OK;
     }
     if (!x || !z || !dy || !W || !ghat) return sd::set_error(SD_E_INVALID, "gl_train_backward: null input");
@@ -894,11 +888,11 @@ int sd_gl_train_backward(const float* x, const float* z, const float* dy, const 
         else
             hipLaunchKernelGGL(sd::k_dghat_part<2>, dim3((unsigned)chunks), dim3(256), 0, s, dy, z, part, rows, J, N,
                                sd::kDghatRows);
-        TR_HIP(hipGetLastError());
-        TR_HIP(sd::sum_parts(part, (int)chunks, (int64_t)J * J, dghat, s));
+        SD_HIP(hipGetLastError());
+        SD_HIP(sd::sum_parts(part, (int)chunks, (int64_t)J * J, dghat, s));
     }
     if (!dx && !dW && !dbias) return SD_OK;
-    TR_HIP(sd::launch_mix(dy, ghat, dz, rows, J, N, 1, s));
+    SD_HIP(sd::launch_mix(dy, ghat, dz, rows, J, N, 1, s));
     if (dx) {
         GemmArgs g{};
         g.A = dz; g.B = W; g.C = dx; g.bias = nullptr; g.types = tp;
@@ -906,7 +900,7 @@ int sd_gl_train_backward(const float* x, const float* z, const float* dy, const 
         g.am = (int64_t)J * N; g.ak = 1; g.aj = N; g.at = 0;         // A[m][n] = dz[m, j, n]
         g.bk = K; g.bn = 1; g.bj = 0; g.bt = (int64_t)N * K;         // B[n][k] = W[t][n][k]
         g.cm = (int64_t)J * K; g.cz = K; g.cs = 0;                   // C[m][k] = dx[m, j, k]
-        TR_HIP(sd::launch_gemm(g, dim3((unsigned)sd::ceil_div(K, sd::TN), (unsigned)sd::ceil_div(rows, sd::TM), J), s));
+        SD_HIP(sd::launch_gemm(g, dim3((unsigned)sd::ceil_div(K, sd::TN), (unsigned)sd::ceil_div(rows, sd::TM), J), s));
     }
     if (dW) {
         const int splits = sd::splits_for(rows);
@@ -917,18 +911,18 @@ int sd_gl_train_backward(const float* x, const float* z, const float* dy, const 
         g.am = 1; g.ak = (int64_t)J * N; g.aj = N; g.at = 0;         // A[n][r] = dz[r, j, n]
         g.bk = (int64_t)J * K; g.bn = 1; g.bj = K; g.bt = 0;         // B[r][k] = x[r, j, k]
         g.cm = K; g.cz = (int64_t)N * K; g.cs = (int64_t)types * N * K;  // C[n][k] = part[s][t][n][k]
-        TR_HIP(sd::launch_gemm(
+        SD_HIP(sd::launch_gemm(
             g, dim3((unsigned)sd::ceil_div(K, sd::TN), (unsigned)sd::ceil_div(N, sd::TM), types * splits), s));
         const int64_t n = (int64_t)types * N * K;
-        TR_HIP(sd::sum_parts(part, splits, n, dW, s));
+        SD_HIP(sd::sum_parts(part, splits, n, dW, s));
     }
     if (dbias) {
         const int64_t chunks = sd::ceil_div(rows, sd::kRowsPerChunk);
         hipLaunchKernelGGL(sd::k_dbias_part, dim3((unsigned)sd::ceil_div(N, 256), types, (unsigned)chunks), dim3(256), 0,
                            s, dz, tp, part, rows, J, N, types, sd::kRowsPerChunk);
-        TR_HIP(hipGetLastError());
+        SD_HIP(hipGetLastError());
         const int64_t n = (int64_t)types * N;
-        TR_HIP(sd::sum_parts(part, (int)chunks, n, dbias, s));
+        SD_HIP(sd::sum_parts(part, (int)chunks, n, dbias, s));
     }
     return SD_OK;
 }
@@ -1037,7 +1031,7 @@ int sd_rmsnorm_backward(const float* x, const float* g, const float* dnorm, cons
     if (R < 0 || C < 1 || C > sd::kRmsMaxC) return sd::set_error(SD_E_INVALID, "sd_rmsnorm_backward: 1 <= C <= 1024");
     hipStream_t s = (hipStream_t)stream;
     if (R == 0) {
-        if (dg) TR_HIP(hipMemsetAsync(dg, 0, (size_t)C * sizeof(float), s));
+        if (dg) SD_HIP(hipMemsetAsync(dg, 0, (size_t)C * sizeof(float), s));
         return SD_OK;
     }
     if (!x || !g || !dnorm || !dy || !dx || !dg) return sd::set_error(SD_E_INVALID, "sd_rmsnorm_backward: null buffer");
@@ -1048,8 +1042,8 @@ int sd_rmsnorm_backward(const float* x, const float* g, const float* dnorm, cons
     float* part = (float*)workspace;
     hipLaunchKernelGGL(sd::k_rmsnorm<true>, dim3((unsigned)blocks), dim3(256), 0, s, x, g, dy, dx, (float*)dnorm, part, R,
                        C, scale, eps);
-    TR_HIP(hipGetLastError());
-    TR_HIP(sd::sum_parts(part, (int)blocks, C, dg, s));
+    SD_HIP(hipGetLastError());
+    SD_HIP(sd::sum_parts(part, (int)blocks, C, dg, s));
     return SD_OK;
 }
 
@@ -1064,7 +1058,7 @@ int sd_mahalanobis_loss_forward(const float* model_out, const float* target, con
     if (rows > 0x7fffffffLL) return sd::set_error(SD_E_INVALID, "sd_mahalanobis_loss_forward: too many rows");
     const size_t lds = sd::mahalanobis_lds(J, F);
     if (lds > 64 * 1024)
-        TR_HIP(hipFuncSetAttribute((const void*)sd::k_mahalanobis<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        SD_HIP(hipFuncSetAttribute((const void*)sd::k_mahalanobis<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)lds));
     hipLaunchKernelGGL(sd::k_mahalanobis<false>, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream, model_out,
                        target, S, t, T, (const float*)nullptr, loss, J, F, pred_noise ? -1.f : 1.f, mse);
@@ -1083,7 +1077,7 @@ int sd_mahalanobis_loss_backward(const float* model_out, const float* target, co
     if (rows > 0x7fffffffLL) return sd::set_error(SD_E_INVALID, "sd_mahalanobis_loss_backward: too many rows");
     const size_t lds = sd::mahalanobis_lds(J, F);
     if (lds > 64 * 1024)
-        TR_HIP(hipFuncSetAttribute((const void*)sd::k_mahalanobis<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        SD_HIP(hipFuncSetAttribute((const void*)sd::k_mahalanobis<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)lds));
     hipLaunchKernelGGL(sd::k_mahalanobis<true>, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream, model_out,
                        target, S, t, T, dloss, dmodel_out, J, F, pred_noise ? -1.f : 1.f, mse);

@@ -537,3 +537,37 @@ def test_f16_range_exact_in_kernel(case, cuda):
         img64, _ = O.p_sample_loop(sd64, cfg, bufs64, start.double(), samp.double(), x_cond=big.double())
         err, err_exact = _max_err(img, img64), _max_err(img_exact, img64)
         assert err <= max(1.5 * err_exact, TOL), (case, scale, err, err_exact)
+
+
+def test_narrow_attention_row_chains(cuda):
+    """A Denoiser whose to_qkv is narrower than its residual stream (attn_heads = 1, attn_dim_head =
+    32: 3 hid = 96 < H = 192), 64 rows, T = 10.  The split route's pre-mix Y scratch is the qkv buffer
+    at H floats per (row, node): two row chains each keep their own part of it (the layout's
+    deterministic check is tests/test_workspace_layout_host.py), so every recorded step equals one
+    chain's bit for bit, eager and graph, and one chain agrees with the oracle."""
+    import dataclasses
+
+    z = golden("release_h36m16_T10")
+    d = build_release_diffusion(z, cuda, attn_heads=1, attn_dim_head=32)
+    xcs, fu, start, samp = release_inputs(z)
+    rows = 64
+    idx = torch.arange(rows) % start.shape[0]  # the fixture's rows, tiled to 64
+    xc, start, samp = xcs.repeat_interleave(fu, 0)[idx], start[idx], samp[idx]
+    eng = d.engine
+    kw = dict(x_cond=xc.to(cuda), start_noise=start.to(cuda), sampling_noise=samp.to(cuda), record=(False, True))
+    eng.set_option("row_chains", 1)
+    one = eng.sample_loop(rows, graph=False, **kw)
+    img1, imgs1 = one[0].clone(), one[4].clone()
+    assert eng.get_option("last_chains") == 1
+    eng.set_option("row_chains", 2)
+    for graph in (False, True, True):
+        two = eng.sample_loop(rows, graph=graph, **kw)
+        torch.cuda.synchronize()
+        assert eng.get_option("last_chains") == 2
+        assert torch.equal(two[0], img1) and torch.equal(two[4], imgs1), graph
+    sd, cfg, bufs = _oracle_setup(d)
+    cfg = dataclasses.replace(cfg, heads=1, dim_head=32)
+    ref, _, ref_imgs = O.p_sample_loop(sd, cfg, bufs, start, samp, x_cond=xc, record_imgs=True)
+    assert _max_err(img1, ref) < TOL, _max_err(img1, ref)
+    for k in range(ref_imgs.shape[1]):  # (rows, T - 1, J, D)
+        assert _max_err(imgs1[:, k], ref_imgs[:, k]) < TOL, (k, _max_err(imgs1[:, k], ref_imgs[:, k]))
