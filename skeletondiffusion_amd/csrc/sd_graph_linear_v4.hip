@@ -30,6 +30,7 @@
 #include <cmath>
 
 #include "sd_gl4_args.h"
+#include "sd_gl4_lds.h"
 #include "sd_internal.h"
 #include "sd_ystore_map.h"
 
@@ -230,11 +231,11 @@ static_assert(sizeof(YOut) == sizeof(GL4GArgs), "YOut: the GEMM-phase block");
 // epilogue (acc * unscale * rms + bias) is unchanged and the tile is f32-accurate for any finite
 // input.  Taken only by the waves whose operands left the f16 range (wave-uniform ballot), so
 // the in-range path keeps its arithmetic and its bitwise route equalities.
-// Placement matters: run while the accumulators are live (before the epilogue), its loop raised the
-// register count of every caller (k_gl4t 163 -> 235 VGPRs; the one-kernel J = 17 / 21 tiles
-// spilled 4-8x more), as a call with acc live too (the live values move to callee-saved
-// registers).  So the callers run it AFTER their normal stores, in a rolled loop over the tiles,
-// inlined (no call frame, no scratch), and store the exact tile over the first.
+// Placement: run while the accumulators are live, its loop raises the caller's register count (k_gl4t
+// 163 -> 235 VGPRs; as a call too).  The GEMM phases (k_gl4t, k_gl4y) therefore run it AFTER their normal
+// stores, in a rolled loop over the tiles, inlined, and store the exact tile over the first.  The
+// one-kernel tiles (gl4_body MODE 0 / 1) cannot: their accumulators feed the epilogue of the same kernel,
+// so they run it BEFORE the epilogue with acc live and pay in registers (spills at J = 17 / 21).
 // SWAP: the operands exchanged (weights as A, x as B), so the tile comes back transposed, in the
 // GEMM phases' store layout (sd_ystore_map.h: lane = row l32, register 4 g + e = column 8 g + 4 h + e);
 // per element the same products in the same k order, so the same bits.
@@ -805,19 +806,14 @@ template <int J, int NW, int NPW, bool FROM_YS = false, class A = GLArgs>  // A:
 __device__ __forceinline__ void attention_epilogue(const A& p, floatx16 (&acc)[NPW][1][3], float* smem,
                                                    const float* sG, int64_t row0, int head, int wave, int lane,
                                                    int q8only = 0) {
-    constexpr int COLS = 96;
+    constexpr Gl4Lds L = gl4_lds(J, 3, FROM_YS ? 3 : 1, 0, 0);  // strides and the Z origin (sd_gl4_lds.h)
+    constexpr int COLS = L.COLS, YS8 = L.YS8, ZN = L.ZN, ZR = L.ZR;
     constexpr int JT = (J + 15) / 16;   // 16-node tiles (k_attention<JT>)
     constexpr int KS = (J + 3) / 4;     // 4-deep k steps of the mixing GEMM
-    constexpr int YS8 = 8 * COLS + 16;  // floats per node in an 8-row Y slab (+16: bank shift)
-    constexpr int ZN = 100;             // floats per node in a Z row (+4: bank shift)
-    constexpr int ZR = J * ZN;          // floats per Z row
     const int l32 = lane & 31, h = lane >> 5, lr = lane & 15, lg = lane >> 4;
     const int hid = p.attn_heads * 32;
-    float* sY = smem;
-    // FROM_YS (MODE 3): Z overwrites the Y slab (mixed into registers first, one barrier between),
-    // so the workgroup needs max(Y, Z) instead of Y + Z: 52 KB at J = 16, 54 KB at J = 17 -- under
-    // 64 KB, two workgroups per CU instead of one holding the whole CU
-    float* sZ = FROM_YS ? smem : smem + J * YS8;
+    float* sY = smem + L.sY;
+    float* sZ = smem + L.sZ;  // FROM_YS (MODE 3): over the Y slab, which is mixed into registers first
     float ga[JT][KS];  // G-hat^T[k = j = 4s + lg][col = i = 16 it + lr]
 #pragma unroll
     for (int it = 0; it < JT; ++it)
@@ -1037,28 +1033,23 @@ __device__ __forceinline__ void gl4_body(const A& p, const int bx, const int nwg
     constexpr int NPW = (J + NW - 1) / NW;  // nodes per wave
     constexpr int KS = (J + 3) / 4;         // 4-deep k steps of the mixing GEMM (K = J padded)
     constexpr int IB = (J + 15) / 16;       // 16-row i blocks of the mixing GEMM
-    constexpr int COLS = 32 * CT;
-    constexpr int YR = COLS + 4;            // floats per Y row (+4: 4x4 blocks read conflict-free)
-    constexpr int YS = 16 * YR + 16;        // floats per node in a 16-row Y slab (+16: bank shift)
+    constexpr Gl4Lds LC = gl4_lds(J, CT, MODE, PREC, 0);  // the strides (sd_gl4_lds.h)
+    constexpr int COLS = LC.COLS, YR = LC.YR, YS = LC.YS, YS8 = LC.YS8, TILE_H = LC.tile_h;  // (YS8: MODE 3's slab, as attention_epilogue)
     constexpr int NTH = NW * 64;
     constexpr int BPW = (COLS + NW - 1) / NW;  // 16-wide mixing blocks per wave per slab
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l32 = lane & 31, h = lane >> 5, lr = lane & 15, lg = lane >> 4;
-    constexpr int TILE_H = PREC ? 512 : 1024;   // halves of one 32-column tile per k chunk (hi | hi+lo)
-    int stage_h = 0;  // halves per weight stage
-    if constexpr (MODE < 2) stage_h = p.ntypes * CT * TILE_H;
-    const int wfl = stage_h;                   // two stages of halves = stage_h floats
+    int ntypes = 0;  // (the split route's argument block has no weight stages)
+    if constexpr (MODE < 2) ntypes = p.ntypes;
+    const Gl4Lds LR = gl4_lds(J, CT, MODE, PREC, ntypes);  // ... and the regions behind the weight stages
     constexpr bool ATT = MODE == 1 || MODE == 3;
-    // Y slab (+ Z rows; MODE 3: Z overwrites Y, attention_epilogue<…, FROM_YS>)
-    const int yfl = MODE == 3 ? max(J * (8 * COLS + 16), 8 * J * 100) : ATT ? J * (8 * COLS + 16) + 8 * J * 100 : J * YS;
     _Float16* sW0 = reinterpret_cast<_Float16*>(smem);
-    _Float16* sW1 = sW0 + stage_h;
-    float* sY = smem;  // aliases the weight stages after the K loop
-    float* sG = smem + (wfl > yfl ? wfl : yfl);
-    float* sF = sG + J * J;  // FiLM (scale + 1 | shift) for this workgroup's columns
+    _Float16* sW1 = sW0 + LR.stage_h;
+    float* sY = smem + LC.sY;  // aliases the weight stages after the K loop
+    float* sG = smem + LR.sG;
+    float* sF = smem + LR.sF;  // FiLM (scale + 1 | shift) for this workgroup's columns
 
-    const int xcd = bx & 7, q8 = nwg >> 3, r8 = nwg & 7;
     // XCD-aware order: consecutive L (the column tiles of one row tile) on one XCD, so x is
     // fetched into that XCD's L2 once.  attn_order 1 (fused attention): L = blockIdx, i.e. head
     // h = blockIdx % heads runs on XCD h % 8 and each XCD's L2 keeps only its heads' weights.
@@ -1073,8 +1064,8 @@ __device__ __forceinline__ void gl4_body(const A& p, const int bx, const int nwg
         fast_divmod((uint32_t)L, p.ntc, q, r);
         ctile = (int)r;
         row0 = (int64_t)q * 32;
-        (void)xcd; (void)q8; (void)r8;
     } else {
+        const int xcd = bx & 7, q8 = nwg >> 3, r8 = nwg & 7;
         const int ntile_c = ATT ? p.attn_heads : (p.N + COLS - 1) / COLS;
         L = (MODE == 1 && p.attn_order == 1) ? (int)bx : (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bx >> 3);
         ctile = L % ntile_c;
@@ -1160,13 +1151,10 @@ __device__ __forceinline__ void gl4_body(const A& p, const int bx, const int nwg
         // split-route phase 2: the slab's Y (from phase 1's p.zs), G-hat and FiLM all loaded to
         // registers first (one memory round trip), then to LDS, one barrier
         constexpr int C4 = COLS / 4;
-        constexpr int YQ = MODE == 2 ? J * 16 * C4 : J * 8 * 24;  // 16-B pieces of the slab
+        constexpr int YQ = J * (MODE == 2 ? 16 : 8) * C4;  // 16-B pieces of the slab (16 or 8 rows)
         constexpr int NYL = (YQ + NTH - 1) / NTH, NGL = (J * J + NTH - 1) / NTH;
-        constexpr int YS8 = 8 * COLS + 16;  // MODE 3: attention_epilogue's slab layout
-        const int64_t tb = (row0 >> 5) * J;
         // column-tiled zs (zs_off, sd_ystore_map.h): consecutive q read consecutive 16-B pieces -- one
         // node's rows of the slab in one column tile are four contiguous runs (one per 8 columns)
-        (void)tb;
         auto ysrc = [&](int q, float*& dst) -> const float* {
             if constexpr (MODE == 2) {
                 static_assert(MODE != 2 || COLS == 32, "MODE 2: one 32-column tile");
@@ -1439,12 +1427,9 @@ __device__ __forceinline__ void gl4_body(const A& p, const int bx, const int nwg
         }
     }
     // f16 range guard: a wave whose f16 operands reached |x| >= 65504 (x_hi would be inf) recomputes
-    // its tiles on exact-f32 MFMA (exact_tile_f32, the split-route GEMM phases' fallback) before the
-    // epilogue, whatever the f16 precision mode (round 6: the one-kernel tiles -- SD_OPT_SPLIT_ROUTE
-    // 1, a gl4_tile option, half precision's J = 16 full-batch default -- only set the status bit
-    // before).  The branch is wave-uniform and never taken in range, so the in-range arithmetic and
-    // every bitwise route equality are unchanged; with the accumulators live the recompute costs
-    // these tiles registers (spills at J = 17 / 21), which only a wave that left the range executes.
+    // its tiles on exact-f32 MFMA before the epilogue, whatever the f16 precision mode (placement:
+    // see exact_tile_f32).  The branch is wave-uniform and never taken in range, so the in-range
+    // arithmetic and every bitwise route equality are unchanged.
     if constexpr (PREC != 2) {
         if (__builtin_amdgcn_ballot_w64(amx >= 65504.0f) != 0) {
             if (p.status && lane == 0) atomicOr(p.status, 1u);
@@ -1531,8 +1516,7 @@ __device__ __forceinline__ void gl4_body(const A& p, const int bx, const int nwg
         }
         // per group of PG blocks: phase 1 every LDS read, phase 2 the mixing MFMAs, phase 3
         // FiLM / tanh / residual / 16-B stores -- no dependent chain per block
-        constexpr int PG = (IB == 1 && BPW <= 8) ? BPW : (BPW < 4 ? BPW : 4);
-        static_assert(PG == PG0, "residual group size");
+        constexpr int PG = PG0;
 #pragma unroll
         for (int k0 = 0; k0 < BPW; k0 += PG) {
             if (!RES_EARLY && p.res) load_res(hc, k0, min(PG, BPW - k0));
@@ -1617,82 +1601,81 @@ __global__ __launch_bounds__(512, 1) void k_gl4_pair(const GL4PairArgs pp) {
     else gl4_body<J, 8, 1, 1, false, 2, PREC, 0>(pp.b, (int)(((tr * ntb + pt - nta) << 1) | slab), 0, smem);
 }
 
-// The split route's mixing phase as a kernel of its own: MODE 2 (one 32-column tile) / MODE 3 (a head's
-// q | k | v tiles) of gl4_body on the compact argument block
+// The split route's phase 2 as a kernel of its own: gl4_body MODE 2 / 3 on the compact argument block
 template <int J, int MODE, int PREC>
 __global__ __launch_bounds__(512, 1) void k_gl4m(const GL4MArgs p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     gl4_body<J, 8, 1, MODE == 3 ? 3 : 1, false, MODE, PREC, 0>(p, blockIdx.x, 0, smem);
 }
 
-// v4 weight staging (GLArgs::gl4_stage): 0 = LDS-DMA stages, 1 = register-staged stages (2, a
-// round-2 diagnostic setting, is now the same as 0: every launch takes its exact LDS).
+// ---- host dispatch ----------------------------------------------------------------------------
+// What every v4 kernel needs of a layer: split weights, K1 and K2 multiples of 16 and an even number
+// of 16-deep chunks (the K loop is unrolled by 2); graph-linear layers also read a row-blocked x1 undivided
+static bool v4_layer_ok(const GLArgs& a) { return a.wsp && (a.K1 + a.K2) % 32 == 0 && a.K1 % 16 == 0; }
+static bool v4_x1_ok(const GLArgs& a) { return !(a.x1_blk && a.x1_div != 1); }
+// 16-B pieces in the epilogue: buffers and row strides 16-B aligned
+static bool v4_epilogue_aligned(const GLArgs& a) {
+    return !(((uintptr_t)a.out & 15) || ((uintptr_t)a.res & 15) || (a.res && (a.res_rs & 3)) || (a.out_rs & 3));
+}
+// f(std::integral_constant<int, J>) for the node counts the v4 tiles are built for
+template <class F>
+static hipError_t with_J(int J, F&& f) {
+    switch (J) {
+        case 16: return f(std::integral_constant<int, 16>{});
+        case 17: return f(std::integral_constant<int, 17>{});
+        case 21: return f(std::integral_constant<int, 21>{});
+        default: return hipErrorNotSupported;
+    }
+}
+static bool v4_has_J(int J) { return with_J(J, [](auto) { return hipSuccess; }) == hipSuccess; }
 
 template <int J, int NW, int RT, int CT, int MODE = 0, int PREC = 0, int STG = 0>
-static hipError_t gl4_launch_t(const GLArgs& a, bool rms, hipStream_t s);
-
-template <int J, int NW, int RT, int CT, int MODE = 0, int PREC = 0>
-static hipError_t gl4_launch(const GLArgs& a, bool rms, hipStream_t s) {
-    constexpr int TILE_H = PREC ? 512 : 1024;
-    // register staging: not for the J > 16 fused attention tile (3 nodes per wave: it would spill)
-    if constexpr (MODE == 0 || (MODE == 1 && J <= 16)) {
-        if (a.gl4_stage == 1 && a.ntypes * CT * (TILE_H / 8) <= 8 * NW * 64)
-            return gl4_launch_t<J, NW, RT, CT, MODE, PREC, 1>(a, rms, s);
-    }
-    return gl4_launch_t<J, NW, RT, CT, MODE, PREC, 0>(a, rms, s);
-}
-
-template <int J, int NW, int RT, int CT, int MODE, int PREC, int STG>
 static hipError_t gl4_launch_t(const GLArgs& a, bool rms, hipStream_t s) {
     constexpr int COLS = 32 * CT;
-    constexpr bool ATT = MODE == 1 || MODE == 3;
-    const int ntile_c = ATT ? a.attn_heads : (a.N + COLS - 1) / COLS;
+    const int ntile_c = MODE == 1 || MODE == 3 ? a.attn_heads : (a.N + COLS - 1) / COLS;
     const int64_t ntile_r = (a.B + 32 * RT - 1) / (32 * RT);
     const dim3 grid((unsigned)(ntile_c * ntile_r * (MODE == 2 ? 2 : MODE == 3 ? 4 : 1)));
-    const size_t wfl = MODE >= 2 ? 0 : (size_t)a.ntypes * CT * (PREC ? 512 : 1024);  // two stages of halves, in floats
-    const size_t yfl = MODE == 3 ? std::max((size_t)J * (8 * COLS + 16), (size_t)8 * J * 100)
-                       : ATT     ? (size_t)J * (8 * COLS + 16) + 8 * J * 100
-                                 : (size_t)J * (16 * (COLS + 4) + 16);
-    size_t lds = ((wfl > yfl ? wfl : yfl) + (size_t)J * J + 2 * COLS) * sizeof(float);
-    if (lds > 160 * 1024) return hipErrorNotSupported;
-    // Every launch takes exactly the LDS it uses and may share its CU with other kernels' workgroups
-    // (row chains, concurrent plans): the co-residency hazard of rounds 1-2 was the packed-FP32
-    // instructions of the co-resident update kernel, not these tiles (build.py).
+    const size_t lds = gl4_lds(J, CT, MODE, PREC, a.ntypes).bytes;
+    if (lds > kGl4LdsMax) return hipErrorNotSupported;
+    // Every launch takes exactly the LDS it uses and may share its CU with other kernels' workgroups (row
+    // chains, concurrent plans): the hazard there was the update kernel's packed FP32
+    auto launch = [&](auto k, const auto& args, unsigned route) {
+        if (lds > kGl4LdsDefault) {
+            hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+        }
+        g_route_bits |= route;
+        hipLaunchKernelGGL(k, grid, dim3(NW * 64), lds, s, args);
+        return hipGetLastError();
+    };
     if constexpr (MODE >= 2) {  // the split route's mixing phase: its own compact argument block
         static_assert(NW == 8 && RT == 1 && STG == 0 && CT == (MODE == 3 ? 3 : 1), "k_gl4m's tile");
         GL4MArgs m;
         if (rms || !gl4_grid_ok((int64_t)ntile_c * ntile_r * (MODE == 2 ? 2 : 4)) || !pack_gl4m(a, (uint32_t)ntile_c, &m))
             return hipErrorInvalidValue;
-        auto km = k_gl4m<J, MODE, PREC>;
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)km, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        g_route_bits |= kRouteMixPhase;
-        hipLaunchKernelGGL(km, grid, dim3(NW * 64), lds, s, m);
-        return hipGetLastError();
-    } else {
-        auto kt = rms ? k_gl4<J, NW, RT, CT, true, MODE, PREC, STG> : k_gl4<J, NW, RT, CT, false, MODE, PREC, STG>;
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)kt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        g_route_bits |= MODE == 1 ? kRouteFusedAttn : kRouteOneKernel;
-        hipLaunchKernelGGL(kt, grid, dim3(NW * 64), lds, s, a);
-        return hipGetLastError();
+        return launch(k_gl4m<J, MODE, PREC>, m, kRouteMixPhase);
+    } else
+        return launch(rms ? k_gl4<J, NW, RT, CT, true, MODE, PREC, STG> : k_gl4<J, NW, RT, CT, false, MODE, PREC, STG>, a,
+                      MODE == 1 ? kRouteFusedAttn : kRouteOneKernel);
+}
+
+// v4 weight staging (GLArgs::gl4_stage): 1 = register-staged stages, any other value LDS-DMA stages
+template <int J, int NW, int RT, int CT, int MODE = 0, int PREC = 0>
+static hipError_t gl4_launch(const GLArgs& a, bool rms, hipStream_t s) {
+    // not for the J > 16 fused attention tile (3 nodes per wave: it would spill); a thread carries at most 8 pieces
+    if constexpr (MODE == 0 || (MODE == 1 && J <= 16)) {
+        if (a.gl4_stage == 1 && gl4_lds(J, CT, MODE, PREC, a.ntypes).stage_h / 8 <= 8 * NW * 64)
+            return gl4_launch_t<J, NW, RT, CT, MODE, PREC, 1>(a, rms, s);
     }
+    return gl4_launch_t<J, NW, RT, CT, MODE, PREC, 0>(a, rms, s);
 }
 
 // ---- split route (small grids) -------------------------------------------------
-// A one-kernel launch is one workgroup's K-loop latency however few workgroups it has: at 50
-// rows an N = 192 layer is 12 workgroups on 256 CUs.  The split route runs phase 1 (k_gl4y, one
-// wave per (32-row tile, node, 32-column tile): J x more parallel work, no LDS) into the zs
-// scratch and phase 2 (k_gl4 MODE 2: mixing + FiLM / tanh / residual per 16-row slab, or MODE 3:
-// the attention epilogue per 8-row slab).  Same arithmetic in the same order as the one-kernel
-// route, so the results are bitwise identical and the route can follow the shard size.
-// Auto threshold on the rows of the whole sampling call (all row chains; GLArgs::route_rows):
-// kSplitRows (sd_internal.h).
-
+// A one-kernel launch is one workgroup's K-loop latency however few workgroups it has (50 rows, N = 192:
+// 12 workgroups on 256 CUs).  The split route runs phase 1 (k_gl4y / k_gl4t) into the zs scratch and
+// phase 2 (k_gl4m MODE 2: mixing + FiLM / tanh / residual per 16-row slab; MODE 3: the attention epilogue
+// per 8-row slab): the one-kernel route's arithmetic in its order, so bitwise its results.  Auto threshold
+// on the rows of the whole sampling call (all row chains; GLArgs::route_rows): kSplitRows (sd_internal.h).
 // 0: one-kernel route; 1: split route with the per-wave phase 1 (k_gl4y, small grids); 2: split
 // route with the tiled phase 1 (k_gl4t, full batches).  GLArgs::split: 0 auto, 1 never, 2 always
 // (k_gl4y), 3 always (k_gl4t).
@@ -1728,9 +1711,7 @@ static int split_route(const GLArgs& a, bool attn) {
 // the split route launch_graph_linear_v4 gives the layer `a` (0 / 1 / 2 as split_route), for
 // callers that shape work by it before they launch (the row chains' boundaries)
 int graph_linear_split_route(const GLArgs& a) {
-    if (!a.wsp || (a.K1 + a.K2) % 32 || a.K1 % 16 || (a.x1_blk && a.x1_div != 1)) return 0;
-    if (a.J != 16 && a.J != 17 && a.J != 21) return 0;
-    return split_route(a, false);
+    return v4_layer_ok(a) && v4_x1_ok(a) && v4_has_J(a.J) ? split_route(a, false) : 0;
 }
 
 template <bool ROWMAJOR, int PF>
@@ -1820,25 +1801,23 @@ static hipError_t launch_gl4t_v(const GLArgs& a, bool rms, int64_t ntile_r, cons
 template <bool ROWMAJOR>
 static hipError_t launch_gl4t(const GLArgs& a, bool rms, int64_t ntile_r, const YDst& yo, hipStream_t s) {
     const int K = a.K1 + a.K2;
-    if (a.K1 % 16 || (a.x1_div != 1 && a.x1_blk)) return hipErrorNotSupported;
+    if (a.K1 % 16 || !v4_x1_ok(a)) return hipErrorNotSupported;
     if (ROWMAJOR && a.N % 256 == 0 && K == 192 && a.prec != 2) return launch_gl4t_v<8, 12, ROWMAJOR, 1>(a, rms, ntile_r, yo, s);
     // f16 operands, row-blocked x, N = 96 / 192: 2 row tiles x 3 column tiles per wave (row-major x
     // -- the J > 21 path -- keeps 1 x 6: its x fragments are 16-B pieces of rows J K floats apart,
-    // and a second row tile doubled them; MANO N = 192 29.1 vs 26.7 us, profiles/r06h)
-    constexpr bool kRt2 = true;
-    constexpr int kPf = 2, kPf6 = 2;  // chunks in flight of the row-blocked forms (3 / 4 measured no faster)
-    constexpr int PFB = ROWMAJOR ? 2 : kPf, PF6 = ROWMAJOR ? 2 : kPf6;
+    // and a second row tile doubled them; MANO N = 192 29.1 vs 26.7 us, profiles/r06h).  Every form
+    // keeps 2 chunks in flight (3 / 4 measured no faster on the row-blocked forms).
     // a paired launch (GLArgs::pair_n) takes the form of its layers, with twice the column groups
     const int Nt = a.pair_n ? a.pair_n : a.N;
-    if (!ROWMAJOR && kRt2 && a.prec != 2 && Nt <= 192 && Nt % 96 == 0) {
-        if (K == 192) return launch_gl4t_v<3, 12, ROWMAJOR, 2, PFB>(a, rms, ntile_r, yo, s);
-        if (K == 256) return launch_gl4t_v<3, 16, ROWMAJOR, 2, PFB>(a, rms, ntile_r, yo, s);
-        if (K == 384) return launch_gl4t_v<3, 24, ROWMAJOR, 2, PFB>(a, rms, ntile_r, yo, s);
+    if (!ROWMAJOR && a.prec != 2 && Nt <= 192 && Nt % 96 == 0) {
+        if (K == 192) return launch_gl4t_v<3, 12, ROWMAJOR, 2>(a, rms, ntile_r, yo, s);
+        if (K == 256) return launch_gl4t_v<3, 16, ROWMAJOR, 2>(a, rms, ntile_r, yo, s);
+        if (K == 384) return launch_gl4t_v<3, 24, ROWMAJOR, 2>(a, rms, ntile_r, yo, s);
     }
     if (Nt % 192 == 0) {
-        if (K == 192) return launch_gl4t_v<6, 12, ROWMAJOR, 1, PF6>(a, rms, ntile_r, yo, s);
-        if (K == 256) return launch_gl4t_v<6, 16, ROWMAJOR, 1, PF6>(a, rms, ntile_r, yo, s);
-        if (K == 384) return launch_gl4t_v<6, 24, ROWMAJOR, 1, PF6>(a, rms, ntile_r, yo, s);
+        if (K == 192) return launch_gl4t_v<6, 12, ROWMAJOR, 1>(a, rms, ntile_r, yo, s);
+        if (K == 256) return launch_gl4t_v<6, 16, ROWMAJOR, 1>(a, rms, ntile_r, yo, s);
+        if (K == 384) return launch_gl4t_v<6, 24, ROWMAJOR, 1>(a, rms, ntile_r, yo, s);
     } else if (Nt % 96 == 0) {
         if (K == 192) return launch_gl4t_v<3, 12, ROWMAJOR, 1>(a, rms, ntile_r, yo, s);
         if (K == 384) return launch_gl4t_v<3, 24, ROWMAJOR, 1>(a, rms, ntile_r, yo, s);
@@ -1849,39 +1828,32 @@ static hipError_t launch_gl4t(const GLArgs& a, bool rms, int64_t ntile_r, const 
 template <int J>
 static hipError_t gl4_split(const GLArgs& a, bool rms, bool attn, int route, hipStream_t s) {
     const int64_t ntile_r = (a.B + 31) / 32;
-    const int ntc = a.N / 32;
     const ZsStrides zst = zs_strides(J, a.N);  // column-tiled (zs_off)
     const YDst yo{a.zs, 0, zst.y_js, zst.y_ts, zst.y_cs};  // (no row stride: a block is laid out by ystore_zs_piece_off)
     hipError_t e = route == 2 ? launch_gl4t<false>(a, rms, ntile_r, yo, s) : hipErrorNotSupported;
     if (e == hipErrorNotSupported) {
         if (a.prec == 2) return hipErrorNotSupported;  // k_gl4y has no bf16 form
-        e = launch_gl4y<false>(a, rms, ntc, ntile_r, yo, s);
+        e = launch_gl4y<false>(a, rms, a.N / 32, ntile_r, yo, s);
     }
     if (e != hipSuccess) return e;
-    if (a.prec == 2) {  // bf16 residual / output storage (PREC 2 epilogue)
-        if (attn) return gl4_launch_t<J, 8, 1, 3, 3, 2, 0>(a, false, s);
-        return gl4_launch_t<J, 8, 1, 1, 2, 2, 0>(a, false, s);
-    }
-    if (attn) return gl4_launch_t<J, 8, 1, 3, 3, 0, 0>(a, false, s);
-    return gl4_launch_t<J, 8, 1, 1, 2, 0, 0>(a, false, s);
+    if (a.prec == 2)  // bf16 residual / output storage (PREC 2 epilogue)
+        return attn ? gl4_launch_t<J, 8, 1, 3, 3, 2, 0>(a, false, s) : gl4_launch_t<J, 8, 1, 1, 2, 2, 0>(a, false, s);
+    return attn ? gl4_launch_t<J, 8, 1, 3, 3, 0, 0>(a, false, s) : gl4_launch_t<J, 8, 1, 1, 2, 0, 0>(a, false, s);
 }
 
-static hipError_t gl4_split_dispatch(const GLArgs& a, bool rms, bool attn, int route, hipStream_t s) {
-    switch (a.J) {
-        case 16: return gl4_split<16>(a, rms, attn, route, s);
-        case 17: return gl4_split<17>(a, rms, attn, route, s);
-        case 21: return gl4_split<21>(a, rms, attn, route, s);
-        default: return hipErrorNotSupported;
-    }
+// the layer on its split route, if it has one; hipErrorNotSupported: nothing launched, the one-kernel route
+static hipError_t gl4_split_dispatch(const GLArgs& a, bool rms, bool attn, hipStream_t s) {
+    const int route = split_route(a, attn);
+    if (!route) return hipErrorNotSupported;
+    return with_J(a.J, [&](auto Jc) { return gl4_split<decltype(Jc)::value>(a, rms, attn, route, s); });
 }
 
 // ---- paired launch: two sibling layers over one input (final_res_block) ------------------------
-// res_linear and block1 of the final ResnetBlock both read cat(x, r) (K = 384, N = 192).  As two
-// layers the second GEMM phase reads the whole input again and the block costs four dependent
-// launches; as a pair the GEMM phase is one k_gl4t launch over 2 N columns (the column groups of a
-// row group are consecutive u on one XCD: x reaches that L2 once) and the mixing phase one launch
-// over both layers' column tiles.  Per accumulator element nothing changes (the same fragments,
-// scale, bias and MFMA sequence), so the results are bitwise those of the two launches.
+// res_linear and block1 of the final ResnetBlock both read cat(x, r) (K = 384, N = 192).  As two layers the
+// second GEMM phase reads the whole input again and the block costs four dependent launches; as a pair the
+// GEMM phase is one k_gl4t launch over 2 N columns (a row group's column groups are consecutive u on one
+// XCD: x reaches that L2 once) and the mixing phase one launch over both layers' column tiles.  Per
+// accumulator element nothing changes, so the results are bitwise those of the two launches.
 template <int J>
 static hipError_t gl4_pair(const GLArgs& pr, const GLArgs& a, const GLArgs& b, hipStream_t s) {
     const int64_t ntile_r = (pr.B + 31) / 32;
@@ -1893,8 +1865,8 @@ static hipError_t gl4_pair(const GLArgs& pr, const GLArgs& a, const GLArgs& b, h
     const dim3 grid((unsigned)((a.N + b.N) / 32 * ntile_r * 2));
     GL4PairArgs pp;
     if (!pack_gl4_pair(a, b, &pp)) return hipErrorInvalidValue;
-    const size_t lds = ((size_t)J * (16 * 36 + 16) + (size_t)J * J + 64) * sizeof(float);  // gl4_launch_t's MODE 2, CT = 1
-    static_assert((J * (16 * 36 + 16) + J * J + 64) * sizeof(float) <= 64 * 1024, "default dynamic LDS");
+    constexpr size_t lds = gl4_lds(J, 1, 2, 0, 0).bytes;  // k_gl4m's MODE 2 tile (any PREC)
+    static_assert(lds <= kGl4LdsDefault, "default dynamic LDS");
     g_route_bits |= kRouteMixPhase;
     if (pr.prec == 2) hipLaunchKernelGGL((k_gl4_pair<J, 2>), grid, dim3(512), lds, s, pp);
     else hipLaunchKernelGGL((k_gl4_pair<J, 0>), grid, dim3(512), lds, s, pp);
@@ -1902,20 +1874,17 @@ static hipError_t gl4_pair(const GLArgs& pr, const GLArgs& a, const GLArgs& b, h
 }
 
 bool graph_linear_pair_ok(const GLArgs& pr, const GLArgs& a, const GLArgs& b) {
-    if (a.J != 16 && a.J != 17 && a.J != 21) return false;
     const int K = a.K1 + a.K2;
-    if (!pr.wsp || !a.wsp || !b.wsp || !pr.pair_n || a.N != pr.pair_n || b.N != pr.pair_n || pr.N != 2 * pr.pair_n ||
-        pr.wsp_nct * 32 != pr.N || a.N % 192 || (K != 192 && K != 384))
+    if (!v4_has_J(a.J) || !pr.wsp || !v4_layer_ok(a) || !v4_x1_ok(a) || !b.wsp || !pr.pair_n || a.N != pr.pair_n ||
+        b.N != pr.pair_n || pr.N != 2 * pr.pair_n || pr.wsp_nct * 32 != pr.N || a.N % 192 || (K != 192 && K != 384))
         return false;
     for (const GLArgs* g : {&a, &b}) {  // launch_graph_linear_v4's conditions, the same operands
-        if (((uintptr_t)g->out & 15) || ((uintptr_t)g->res & 15) || (g->res && (g->res_rs & 3)) || (g->out_rs & 3)) return false;
-        if (g->x1 != pr.x1 || g->x2 != pr.x2 || g->K1 != pr.K1 || g->K2 != pr.K2 || g->B != pr.B || g->zs != pr.zs ||
-            g->x1_div != pr.x1_div || g->x1_row0 != pr.x1_row0 || g->x1_blk != pr.x1_blk || g->x2_blk != pr.x2_blk ||
-            g->x1_bf16 != pr.x1_bf16 || g->x2_bf16 != pr.x2_bf16 || g->prec != pr.prec || g->zs_n != pr.N)
+        if (!v4_epilogue_aligned(*g) || g->x1 != pr.x1 || g->x2 != pr.x2 || g->K1 != pr.K1 || g->K2 != pr.K2 || g->B != pr.B ||
+            g->zs != pr.zs || g->x1_div != pr.x1_div || g->x1_row0 != pr.x1_row0 || g->x1_blk != pr.x1_blk ||
+            g->x2_blk != pr.x2_blk || g->x1_bf16 != pr.x1_bf16 || g->x2_bf16 != pr.x2_bf16 || g->prec != pr.prec || g->zs_n != pr.N)
             return false;
     }
     if (a.zs_c0 != 0 || b.zs_c0 != a.N) return false;
-    if (K % 32 || a.K1 % 16 || (a.x1_blk && a.x1_div != 1)) return false;
     // the tiled split route for both layers, as each would take alone, and room for 2 N columns of Y
     return split_route(a, false) == 2 && split_route(b, false) == 2 && split_route(pr, false) == 2;
 }
@@ -1923,103 +1892,72 @@ bool graph_linear_pair_ok(const GLArgs& pr, const GLArgs& a, const GLArgs& b) {
 hipError_t launch_graph_linear_pair_v4(const GLArgs& pr, const GLArgs& a, const GLArgs& b, hipStream_t s) {
     if (!graph_linear_pair_ok(pr, a, b)) return hipErrorNotSupported;
     if (pr.B <= 0) return hipSuccess;
-    switch (a.J) {
-        case 16: return gl4_pair<16>(pr, a, b, s);
-        case 17: return gl4_pair<17>(pr, a, b, s);
-        default: return gl4_pair<21>(pr, a, b, s);
+    return with_J(a.J, [&](auto Jc) { return gl4_pair<decltype(Jc)::value>(pr, a, b, s); });
+}
+
+// The one-kernel tile <NW, RT, CT> of a layer: cfg = the gl4_tile option or the plan's hint
+template <int J>
+static hipError_t gl4_one_kernel(const GLArgs& a, bool rms, int cfg, hipStream_t s) {
+    if (a.prec == 2) {  // bf16 mode: row-major operands, the default tiles only
+        if (a.x1_blk || a.x2_blk || a.res_blk || a.out_blk) return hipErrorNotSupported;
+        if constexpr (J == 16) return gl4_launch<16, 8, 1, 3, 0, 2>(a, rms, s);
+        else return gl4_launch<J, 8, 1, 2, 0, 2>(a, rms, s);
+    }
+    if (a.prec == 1) {  // half precision mode: the default tiles only
+        if constexpr (J == 16) return cfg == 812 ? gl4_launch<16, 8, 1, 2, 0, 1>(a, rms, s) : gl4_launch<16, 8, 1, 3, 0, 1>(a, rms, s);
+        else if constexpr (J == 17) return gl4_launch<17, 8, 2, 1, 0, 1>(a, rms, s);
+        else return gl4_launch<21, 8, 1, 2, 0, 1>(a, rms, s);
+    }
+    if constexpr (J == 16) {
+        if (cfg == 422) return gl4_launch<16, 4, 2, 2>(a, rms, s);
+        if (cfg == 412) return gl4_launch<16, 4, 1, 2>(a, rms, s);
+        if (cfg == 421) return gl4_launch<16, 4, 2, 1>(a, rms, s);
+        if (cfg == 821) return gl4_launch<16, 8, 2, 1>(a, rms, s);
+        if (cfg == 812) return gl4_launch<16, 8, 1, 2>(a, rms, s);
+        if (cfg == 813) return gl4_launch<16, 8, 1, 3>(a, rms, s);
+        if (cfg == 811) return gl4_launch<16, 8, 1, 1>(a, rms, s);  // small batches: 3x the workgroups
+        if (cfg == 822) return gl4_launch<16, 8, 2, 2>(a, rms, s);
+        // small grids (a few sequences: config 4, one sequence x 50 futures): 32 x 32 tiles give
+        // 3x the workgroups of 32 x 96 and a third of the per-workgroup weight bytes; measured
+        // 1.69x (59.0 vs 34.9 futures/s at 50 rows, T = 1000), but 0.91x at B = 3200
+        if (cfg == 0 && (a.B + 31) / 32 * ((a.N + 95) / 96) < 32) return gl4_launch<16, 8, 1, 1>(a, rms, s);
+        // 32 rows x 96 columns: 200 workgroups for an N = 192 layer at B = 3200 (64 x 64 gives
+        // 150, leaving 40 % of the CUs idle); measured 1.28x faster on those layers
+        return gl4_launch<16, 8, 1, 3>(a, rms, s);
+    } else {  // J > 16 needs two 16-node blocks in the mixing epilogue: 96 columns spill there
+        if (J == 17 && cfg == 821) return gl4_launch<17, 8, 2, 1>(a, rms, s);
+        if (cfg == 813) return gl4_launch<J, 8, 1, 3>(a, rms, s);
+        return gl4_launch<J, 8, 1, 2>(a, rms, s);
     }
 }
 
 hipError_t launch_graph_linear_v4(const GLArgs& a, bool rms, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;
-    // K1, K2 multiples of 16 and an even number of 16-deep chunks (the K loop is unrolled by 2)
-    // 16-B row segments in the epilogue: N, row strides and buffers 16-B aligned
-    if ((a.N & 3) || ((uintptr_t)a.out & 15) || ((uintptr_t)a.res & 15) || (a.res && (a.res_rs & 3)) || (a.out_rs & 3))
-        return hipErrorNotSupported;
-    if (!a.wsp || (a.K1 + a.K2) % 32 || a.K1 % 16 || (a.x1_blk && a.x1_div != 1)) return hipErrorNotSupported;
-    if (a.J == 16 || a.J == 17 || a.J == 21)
-        if (const int route = split_route(a, false)) {
-            const hipError_t e = gl4_split_dispatch(a, rms, false, route, s);
-            if (e != hipErrorNotSupported) return e;  // else: nothing launched, the one-kernel route
-        }
+    if ((a.N & 3) || !v4_epilogue_aligned(a) || !v4_layer_ok(a) || !v4_x1_ok(a)) return hipErrorNotSupported;  // (N: 16-B row segments)
+    const hipError_t e = gl4_split_dispatch(a, rms, false, s);
+    if (e != hipErrorNotSupported) return e;
     if (a.ln_w) return hipErrorNotSupported;  // the Block LayerNorm lives in the split mixing phase only
-    const int cfg = a.gl4_cfg ? a.gl4_cfg : a.tile_hint;
-    if (a.prec == 2) {  // bf16 mode: row-major operands, the default tiles only
-        if (a.x1_blk || a.x2_blk || a.res_blk || a.out_blk) return hipErrorNotSupported;
-        switch (a.J) {
-            case 16: return gl4_launch<16, 8, 1, 3, 0, 2>(a, rms, s);
-            case 17: return gl4_launch<17, 8, 1, 2, 0, 2>(a, rms, s);
-            case 21: return gl4_launch<21, 8, 1, 2, 0, 2>(a, rms, s);
-            default: return hipErrorNotSupported;
-        }
-    }
-    if (a.prec == 1) {  // half precision mode: the default tiles only
-        switch (a.J) {
-            case 16:
-                if (cfg == 812) return gl4_launch<16, 8, 1, 2, 0, 1>(a, rms, s);
-                return gl4_launch<16, 8, 1, 3, 0, 1>(a, rms, s);
-            case 17: return gl4_launch<17, 8, 2, 1, 0, 1>(a, rms, s);
-            case 21: return gl4_launch<21, 8, 1, 2, 0, 1>(a, rms, s);
-            default: return hipErrorNotSupported;
-        }
-    }
-    switch (a.J) {
-        case 16:
-            if (cfg == 422) return gl4_launch<16, 4, 2, 2>(a, rms, s);
-            if (cfg == 412) return gl4_launch<16, 4, 1, 2>(a, rms, s);
-            if (cfg == 421) return gl4_launch<16, 4, 2, 1>(a, rms, s);
-            if (cfg == 821) return gl4_launch<16, 8, 2, 1>(a, rms, s);
-            if (cfg == 812) return gl4_launch<16, 8, 1, 2>(a, rms, s);
-            if (cfg == 813) return gl4_launch<16, 8, 1, 3>(a, rms, s);
-            if (cfg == 811) return gl4_launch<16, 8, 1, 1>(a, rms, s);  // small batches: 3x the workgroups
-            if (cfg == 822) return gl4_launch<16, 8, 2, 2>(a, rms, s);
-            // small grids (a few sequences: config 4, one sequence x 50 futures): 32 x 32 tiles give
-            // 3x the workgroups of 32 x 96 and a third of the per-workgroup weight bytes; measured
-            // 1.69x (59.0 vs 34.9 futures/s at 50 rows, T = 1000), but 0.91x at B = 3200
-            if (cfg == 0 && (a.B + 31) / 32 * ((a.N + 95) / 96) < 32) return gl4_launch<16, 8, 1, 1>(a, rms, s);
-            // 32 rows x 96 columns: 200 workgroups for an N = 192 layer at B = 3200 (64 x 64 gives
-            // 150, leaving 40 % of the CUs idle); measured 1.28x faster on those layers
-            return gl4_launch<16, 8, 1, 3>(a, rms, s);
-        // J > 16 needs two 16-node blocks in the mixing epilogue: 96 columns spill there
-        case 17:
-            if (cfg == 821) return gl4_launch<17, 8, 2, 1>(a, rms, s);
-            if (cfg == 813) return gl4_launch<17, 8, 1, 3>(a, rms, s);
-            return gl4_launch<17, 8, 1, 2>(a, rms, s);
-        case 21:
-            if (cfg == 813) return gl4_launch<21, 8, 1, 3>(a, rms, s);
-            return gl4_launch<21, 8, 1, 2>(a, rms, s);
-        default: return hipErrorNotSupported;
-    }
+    return with_J(a.J, [&](auto Jc) { return gl4_one_kernel<decltype(Jc)::value>(a, rms, a.gl4_cfg ? a.gl4_cfg : a.tile_hint, s); });
 }
 
-// to_qkv (RMSNorm-scaled, no bias) + Attention fused; a.out = (B, J, heads * 32) attention
-// output.  hipErrorNotSupported where the fused tile does not apply (caller falls back to the
-// graph-linear + k_attention pair).
+// to_qkv (RMSNorm-scaled, no bias) + Attention fused; a.out = (B, J, heads * 32) attention output.
+// hipErrorNotSupported where the fused tile does not apply (caller: graph-linear + k_attention).
 hipError_t launch_qkv_attention_v4(const GLArgs& a, bool rms, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;
-    if (!a.wsp || a.J > 32 || a.attn_heads < 1 || a.N != 3 * a.attn_heads * 32 || a.bias || a.film || a.res ||
-        a.act || (a.K1 + a.K2) % 32 || a.K1 % 16 || ((uintptr_t)a.out & 15) || (a.out_rs & 3))
+    if (!v4_layer_ok(a) || !v4_epilogue_aligned(a) || a.attn_heads < 1 || a.N != 3 * a.attn_heads * 32 || a.bias || a.film ||
+        a.res || a.act)
         return hipErrorNotSupported;
     GLArgs b = a;
     b.attn_order = a.gl4_cfg == 100 ? 1 : 0;
-    if (a.J == 16 || a.J == 17 || a.J == 21)
-        if (const int route = split_route(a, true)) {
-            const hipError_t e = gl4_split_dispatch(b, rms, true, route, s);
-            if (e != hipErrorNotSupported) return e;
-        }
-    // J = 17 / 21: 3 nodes per wave, two 16-node tiles in the softmax
-    switch (a.J) {
-        case 16:
-            if (a.prec == 2) return gl4_launch<16, 8, 1, 3, 1, 2>(b, rms, s);
-            return a.prec == 1 ? gl4_launch<16, 8, 1, 3, 1, 1>(b, rms, s) : gl4_launch<16, 8, 1, 3, 1>(b, rms, s);
-        case 17:
-            if (a.prec == 2) return gl4_launch<17, 8, 1, 3, 1, 2>(b, rms, s);
-            return a.prec == 1 ? gl4_launch<17, 8, 1, 3, 1, 1>(b, rms, s) : gl4_launch<17, 8, 1, 3, 1>(b, rms, s);
-        case 21:  // 13 node types: 2 x 78 KB weight stages + G-hat + FiLM = 158.5 KB of LDS
-            if (a.prec == 2) return gl4_launch<21, 8, 1, 3, 1, 2>(b, rms, s);
-            return a.prec == 1 ? gl4_launch<21, 8, 1, 3, 1, 1>(b, rms, s) : gl4_launch<21, 8, 1, 3, 1>(b, rms, s);
-        default: return hipErrorNotSupported;
-    }
+    const hipError_t e = gl4_split_dispatch(b, rms, true, s);  // (the route does not depend on attn_order)
+    if (e != hipErrorNotSupported) return e;
+    // J = 17 / 21: 3 nodes per wave, two 16-node tiles in the softmax (J = 21, 13 node types: 2 x 78 KB
+    // weight stages + G-hat + FiLM = 158.5 KB of LDS)
+    return with_J(a.J, [&](auto Jc) {
+        constexpr int J = decltype(Jc)::value;
+        if (a.prec == 2) return gl4_launch<J, 8, 1, 3, 1, 2>(b, rms, s);
+        return a.prec == 1 ? gl4_launch<J, 8, 1, 3, 1, 1>(b, rms, s) : gl4_launch<J, 8, 1, 3, 1>(b, rms, s);
+    });
 }
 
 }  // namespace sd
