@@ -371,6 +371,49 @@ int sd_cdist(const float* x1, int64_t m, const float* x2, int64_t n, int64_t fea
 int sd_set_mean_distance(const float* dist, int64_t n, const int64_t* row_ptr, const int64_t* col, int64_t nsets,
                          float* out, void* stream);
 
+/* Diversity ranking (reference src/metrics/ranking.py:3-40 greates_minimum_distance / get_highest_diversity /
+ * find_samples_maxapd_wrtGT and :42-63 get_closest_and_nfurthest_maxapd: the notebooks' choice of the futures
+ * to show; there a batched torch.cdist and a Python loop per sequence with .tolist() / .nonzero() per pick).
+ * Per sequence b the points are P_0 = the anchor and P_{1+s} = pred[b, s] (features floats each), and d(i, j)
+ * is sd_cdist's value function above: bitwise symmetric, an exactly zero diagonal, independent of tile,
+ * alignment and operand order.  Farthest-point greedy: C = {0}, m_i = d(i, 0) for i = 1..samples; for
+ * k = 0..n_choose-1 the lowest index c not in C that maximises m_c is picked, idx_out[b, k] = c - 1,
+ * score_out[b, k] = m_c, then c joins C and m_i = min(m_i, d(i, c)).  The comparisons are a total order in
+ * which NaN ranks below every number (two NaNs: the lower index), and the min keeps a NaN: a NaN sample is
+ * picked last.  The reference raises ValueError("No index found") on NaN; a kernel cannot raise.
+ *   from_closest == 0: the anchor is target[b] (find_samples_maxapd_wrtGT).
+ *   from_closest == 1: closest[b] = the first index of the minimum of d(target[b], pred[b, s]), NaN ranking
+ *     above every number, and the anchor is pred[b, closest[b]] (get_closest_and_nfurthest_maxapd); its twin
+ *     among the candidates is at distance exactly 0 and is taken last.
+ *   pred (nseq, samples, features), target (nseq, features)  f32, dense, 4-byte aligned; 16-byte loads where
+ *     both bases are 16-byte aligned and features % 4 == 0
+ *   idx_out (nseq, n_choose) int64; required
+ *   score_out (nseq, n_choose) f32, closest_out (nseq) int64 (from_closest == 1 only), dist_out (nseq,
+ *     samples + 1, samples + 1) f32 = the matrix of [anchor; pred[b]]: each may be NULL
+ *   workspace  sd_diverse_rank_workspace_bytes(nseq, samples) bytes (0 for invalid sizes)
+ * Two launches: the distance matrices (upper triangle in tiles of 32 x 32, mirrored; never a pair of two
+ * sequences), then one workgroup per sequence for the selection (a fixed shuffle tree, no atomics, no host
+ * round trip).  1 <= samples <= 255, 1 <= n_choose <= samples, features >= 1, from_closest 0 or 1, nseq *
+ * tile pairs <= 2^31 - 1 (SD_E_INVALID names the argument, before any launch); nseq == 0 launches nothing. */
+size_t sd_diverse_rank_workspace_bytes(int64_t nseq, int32_t samples);
+int sd_diverse_rank(const float* pred, const float* target, int64_t nseq, int32_t samples, int64_t features,
+                    int32_t n_choose, int32_t from_closest, int64_t* idx_out, float* score_out, int64_t* closest_out,
+                    float* dist_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Class-wise CMD accumulation (reference src/metrics/cmd.py:15-31 resolve_cmd and :34-57 CMDMetricStorer, which
+ * keep every batch's motion profiles on the host): values (rows, width) f32 the batch's motion profiles
+ * (sd_realism's motion_out), cls (rows) int64 DEVICE class indices; the state is updated in place:
+ *   sum (classes, width) f64   += per class the rows' values; each (class, column) adds its rows in ascending
+ *                              row order from the value it holds, so the state after a dataset is bitwise the
+ *                              same however the rows were split into calls
+ *   count (classes) int64      += the class's rows
+ *   total (1) int64            += rows (a class index outside [0, classes) counts here only, as the
+ *                              reference's mask, cmd.py:25-30)
+ * One plain kernel, no atomics.  rows >= 0, width, classes >= 1 and non-NULL pointers (SD_E_INVALID names the
+ * argument, before any launch); rows == 0 launches nothing. */
+int sd_class_sum(const float* values, const int64_t* cls, int64_t rows, int32_t width, int32_t classes, double* sum,
+                 int64_t* count, int64_t* total, void* stream);
+
 /* Test hooks: one kernel on caller buffers, for the per-kernel numerics tests.
  * sd_test_graph_linear: out(B,J,N) = act(FiLM(ghat @ (s_j W[type j] [x1_j | x2_j] + bias[type j]))) + res,
  *   W (types,N,K1+K2), bias (types,N) or NULL, ghat (J,J), film (2N) or NULL, res (B,J,N) or NULL,

@@ -43,7 +43,7 @@ EXPORTED = (
     "sd_pose_loss", "sd_test_set_split_route", "sd_chain_start", "sd_chain_tile_unit", "sd_best_sample",
     "sd_realism_target", "sd_realism", "sd_realism_frame_tile",
     "sd_fid_workspace_bytes", "sd_fid_features", "sd_fid_stats_workspace_bytes", "sd_fid_stats_update",
-    "sd_cdist", "sd_set_mean_distance",
+    "sd_cdist", "sd_set_mean_distance", "sd_diverse_rank_workspace_bytes", "sd_diverse_rank", "sd_class_sum",
     "sd_gru_train_workspace_bytes", "sd_gru_train_forward", "sd_gru_train_backward", "sd_gx_table_forward",
     "sd_gx_table_backward",
     "sd_optim_workspace_bytes", "sd_optim_grad_norm", "sd_optim_adam_step", "sd_optim_ema_update",
@@ -205,6 +205,9 @@ def _declare(lib: ctypes.CDLL) -> None:
         "sd_fid_stats_update": (ctypes.c_int, [vp, i64, i32, vp, vp, sz, vp]),
         "sd_cdist": (ctypes.c_int, [vp, i64, vp, i64, i64, vp, vp]),
         "sd_set_mean_distance": (ctypes.c_int, [vp, i64, vp, vp, i64, vp, vp]),
+        "sd_diverse_rank_workspace_bytes": (sz, [i64, i32]),
+        "sd_diverse_rank": (ctypes.c_int, [vp, vp, i64, i32, i64, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
+        "sd_class_sum": (ctypes.c_int, [vp, vp, i64, i32, i32, vp, vp, vp, vp]),
         "sd_optim_workspace_bytes": (sz, [vp, i32]),
         "sd_optim_grad_norm": (ctypes.c_int, [vp, vp, i32, ctypes.c_float, vp, vp, sz, vp]),
         "sd_optim_adam_step": (ctypes.c_int, [vp, i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, i32, vp, vp]),

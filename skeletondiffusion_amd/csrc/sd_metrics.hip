@@ -364,6 +364,28 @@ __global__ __launch_bounds__(256) void k_best_select(const float* __restrict__ p
     if (tail_out) copy_span(tail_out + b * Lt, src + (L - Lt), Lt, t0, nt);
 }
 
+// Class-wise sums of the CMD (cmd.py:22-29): thread (c, w) goes on from sum[c, w] and adds values[r, w] of
+// the rows r of class c in ascending row order, in float64: one chain per (class, column), so the state
+// after a dataset does not depend on how its rows were cut into calls.  Thread (c, 0) counts the class's
+// rows, thread (0, 0) the rows of the call (a class index outside [0, classes) counts there only).
+__global__ __launch_bounds__(256) void k_class_sum(const float* __restrict__ values, const int64_t* __restrict__ cls,
+                                                   int64_t rows, int width, int classes, double* __restrict__ sum,
+                                                   int64_t* __restrict__ count, int64_t* __restrict__ total) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)classes * width) return;
+    const int c = (int)(e / width), w = (int)(e - (int64_t)c * width);
+    double acc = sum[e];
+    int64_t n = 0;
+    for (int64_t r = 0; r < rows; ++r)
+        if (cls[r] == c) {
+            acc += (double)values[r * width + w];
+            ++n;
+        }
+    sum[e] = acc;
+    if (w == 0) count[c] += n;
+    if (e == 0) total[0] += rows;
+}
+
 }  // namespace
 
 }  // namespace sd
@@ -478,6 +500,25 @@ int sd_best_sample(const float* pred, const float* target, int64_t nseq, int32_t
         hipLaunchKernelGGL(k_best_select, dim3((unsigned)nseq, shares), dim3(256), 0, s, pred, per_sample, samples, L, Lt,
                            min_out, idx_out, best_out, tail_out);
     }
+    SD_HIP(hipGetLastError());
+    return SD_OK;
+}
+
+// class-wise CMD accumulation (cmd.py:17-29): the state (sum, count, total) is updated in place
+int sd_class_sum(const float* values, const int64_t* cls, int64_t rows, int32_t width, int32_t classes, double* sum,
+                 int64_t* count, int64_t* total, void* stream) {
+    if (rows < 0) return set_error(SD_E_INVALID, "class_sum: rows must be >= 0");
+    if (width < 1) return set_error(SD_E_INVALID, "class_sum: width must be >= 1");
+    if (classes < 1) return set_error(SD_E_INVALID, "class_sum: classes must be >= 1");
+    if (rows == 0) return SD_OK;
+    if (!values) return set_error(SD_E_INVALID, "class_sum: values is null");
+    if (!cls) return set_error(SD_E_INVALID, "class_sum: cls is null");
+    if (!sum) return set_error(SD_E_INVALID, "class_sum: sum is null");
+    if (!count) return set_error(SD_E_INVALID, "class_sum: count is null");
+    if (!total) return set_error(SD_E_INVALID, "class_sum: total is null");
+    const int64_t cells = (int64_t)classes * width;
+    hipLaunchKernelGGL(k_class_sum, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, (hipStream_t)stream, values, cls, rows,
+                       (int)width, (int)classes, sum, count, total);
     SD_HIP(hipGetLastError());
     return SD_OK;
 }

@@ -8,6 +8,9 @@ and the long-term rollouts (src/eval_utils.py:44-99), with the reference's signa
                                              feed its last observed-length frames back, repeat
     long_term_prediction_best_first50(...)   draw S futures once, then continue each of them
     get_stats_funcs(stats_mode, skeleton_key)   the metric dict of an evaluation loop (src/config_metrics.py:18-53)
+    get_fid_storer / get_apde_storer / get_cmd_storer   the dataset-level storers (config_metrics.py:55-69)
+    metric_set(stats_mode, skeleton_key, ...)   all of them behind update / all_reduce / compute, the result table
+                                             of an evaluation (config_metrics.py:71-96)
 
 `model` is the (autoencoder, diffusion) pair of `prepare_model`.  Every stage is a HIP kernel sequence
 (sd_gru_encode, sd_sample_loop, sd_gru_decode, sd_best_sample); nothing here copies to the host or
@@ -200,6 +203,75 @@ def get_apde_storer(annotations_folder=None, gt_apd=None, device="cuda", **kwarg
     return factory, lambda pred, **kwgs: metrics.apd(pred)
 
 
+def get_cmd_storer(idx_to_class, mean_motion_per_class, if_consider_hip=False, device="cuda", **kwargs):
+    """config_metrics.py:62-69 `get_cmd_storer` without ignite and without the dataset object: (a factory of
+    `metrics.CMDAccumulator` over the dataset's `idx_to_class` / `mean_motion_per_class`, the
+    `(motion_for_cmd(pred), class_idx)` transform of the evaluation dict).  `class_idx` (B,) are the batch's
+    class indices (the reference looks them up from the metadata's class names).  Per batch:
+    `acc.update(*transform(**out))`; at the end `acc.compute()`.  The factory takes and ignores the
+    reference's `output_transform` keyword."""
+    assert not if_consider_hip
+    if len(idx_to_class) != len(mean_motion_per_class):
+        raise ValueError(f"get_cmd_storer: {len(idx_to_class)} classes, {len(mean_motion_per_class)} mean motions")
+
+    def factory(output_transform=None, **kw):
+        return metrics.CMDAccumulator(mean_motion_per_class, device)
+
+    return factory, lambda pred, class_idx, **kwgs: (metrics.motion_for_cmd(pred), class_idx)
+
+
+class MetricSet:
+    """What `metric_set` returns: `storers` maps every name of the result table to its accumulator."""
+
+    def __init__(self, stats_funcs, storers, extra):
+        self.stats_funcs, self.storers, self._extra = stats_funcs, storers, extra
+
+    def update(self, pred=None, target=None, mm_gt=None, obs=None, class_idx=None, segment_idx=None, **kwargs) -> None:
+        """One batch of the evaluation loop: pred (B, S, T, J, 3), target (B, T, J, 3), mm_gt the batch's
+        multimodal ground truths, obs the observation, class_idx (B,) for CMD, segment_idx (optional) for
+        APDE.  Everything is queued on the current stream."""
+        out = dict(pred=pred, target=target, mm_gt=mm_gt, obs=obs, **kwargs)
+        for name, fn in self.stats_funcs.items():
+            self.storers[name].update(fn(**out))
+        if "FID" in self._extra:
+            self.storers["FID"].update(*self._extra["FID"](**out))
+        if "CMD" in self._extra:
+            self.storers["CMD"].update(*self._extra["CMD"](class_idx=class_idx, **out))
+        if "APDE" in self._extra:
+            self.storers["APDE"].update(self._extra["APDE"](**out), segment_idx)
+
+    def all_reduce(self, group=None) -> "MetricSet":
+        for s in self.storers.values():
+            s.all_reduce(group)
+        return self
+
+    def compute(self) -> dict:
+        """name -> Python float: one host copy per storer."""
+        return {name: s.compute() for name, s in self.storers.items()}
+
+
+def metric_set(stats_mode, skeleton_key, dataset_split="test", dataset_name="h36m", if_compute_cmd=False,
+               if_compute_fid=False, if_compute_apde=False, device="cuda", **config) -> MetricSet:
+    """config_metrics.py:71-96 `attach_engine_to_metrics` without ignite: one `metrics.MetricAccumulator` per
+    `get_stats_funcs` entry ('max' where the name contains '_max', else 'avg'), FID for h36m + test +
+    if_compute_fid (`get_fid_storer`: classifier_path / precomputed_folder), CMD for test + if_compute_cmd
+    (`get_cmd_storer`: idx_to_class, mean_motion_per_class), APDE with if_compute_apde (`get_apde_storer`:
+    gt_apd / annotations_folder).  `update(**batch)` per batch, `all_reduce()` across ranks, `compute()` the
+    result table {name: float}."""
+    stats = get_stats_funcs(stats_mode, skeleton_key, **config)
+    storers = {k: metrics.MetricAccumulator("max" if "_max" in k else "avg") for k in stats}
+    extra = {}
+    if dataset_name == "h36m" and dataset_split == "test" and if_compute_fid:
+        storers["FID"], extra["FID"] = get_fid_storer(device=device, **config)
+    if dataset_split == "test" and if_compute_cmd:
+        factory, extra["CMD"] = get_cmd_storer(device=device, **config)
+        storers["CMD"] = factory()
+    if if_compute_apde:
+        factory, extra["APDE"] = get_apde_storer(device=device, **config)
+        storers["APDE"] = factory()
+    return MetricSet(stats, storers, extra)
+
+
 __all__ = ["get_diffusion_latent_codes", "decode_latent_pred", "get_prediction", "process_evaluation_pair",
            "long_term_prediction_best_every50", "long_term_prediction_best_first50", "get_stats_funcs", "get_fid_storer",
-           "get_apde_storer"]
+           "get_apde_storer", "get_cmd_storer", "metric_set", "MetricSet"]

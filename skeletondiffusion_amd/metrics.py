@@ -28,6 +28,13 @@ reduction != 'mean'), reduced in a fixed order (deterministic).
     APDEAccumulator(gt_apd)           apde.py:9-48           update / merge / all_reduce / reset / compute: mean
                                       |APD(pred) - APD(multimodal gt)|; the table: multimodal_gt.MultimodalGT.gt_apd
 
+    diverse_rank(pred, target, n, from_closest)  ranking.py:3-63  farthest-point greedy over each sequence's samples
+                                      (sd_diverse_rank; up to 255 samples), with the reference's
+    find_samples_maxapd_wrtGT(pred, target, num_chosen_samples) and get_closest_and_nfurthest_maxapd(y_pred, y_gt, n)
+    CMDAccumulator(mean_motion_per_class)  cmd.py:15-57    class-wise CMD: float64 sums per class on the device
+                                      (sd_class_sum), update / merge / all_reduce / reset / motion_per_class / compute
+    MetricAccumulator(return_op)      metric_storer.py       mean / max / min of per-sequence values, float64 on the device
+
 Up to 64 samples per sequence (the release evaluation draws 50); up to 64 joints, limbs and angle pairs.
 
 cmd(val_per_frame, val_ref) (multimodal.py:10-13) is the one host-side function here: the CMD score of
@@ -219,7 +226,7 @@ def cmd(val_per_frame, val_ref) -> float:
     """Cumulative motion distribution of one class (multimodal.py:10-13): val_per_frame the class's
     mean motion profile M_t (frames - 1 values: array, list or tensor), val_ref its dataset mean
     motion M: sum_t (T - t) |M_t - M|.  The class-weighted aggregation over a dataset
-    (src/metrics/cmd.py:15-31) stays with the caller, on the host."""
+    (src/metrics/cmd.py:15-31) is `CMDAccumulator`."""
     import numpy as np
 
     v = np.asarray(val_per_frame.detach().cpu() if torch.is_tensor(val_per_frame) else val_per_frame, dtype=np.float64)
@@ -629,7 +636,252 @@ class APDEAccumulator:
         return s / c if c else float("nan")
 
 
+# ---- diversity ranking (sd_diverse_rank) -----------------------------------------------------------
+MAX_RANK_SAMPLES = 255  # sd::rank::kMaxPoints - 1
+DiverseRank = collections.namedtuple("DiverseRank", ["idx", "score", "closest"])
+DiverseRank.__doc__ = """What `diverse_rank` returns: idx (B, n) int64 the picked samples in pick order, score (B, n)
+float32 each pick's distance to the set chosen before it, closest (B,) int64 the sample nearest the target
+(None without from_closest).  Device tensors."""
+
+
+def _rank(pred, target, n, from_closest, want_dist=False):
+    if not torch.is_tensor(pred) or not torch.is_tensor(target) or pred.dim() < 3 or target.dim() != pred.dim() - 1 \
+            or target.shape[0] != pred.shape[0] or tuple(target.shape[1:]) != tuple(pred.shape[2:]):
+        raise ValueError(f"diverse_rank: pred (B, S, ...) and target (B, ...) expected, got "
+                         f"{tuple(getattr(pred, 'shape', ()))} and {tuple(getattr(target, 'shape', ()))}")
+    B, S = int(pred.shape[0]), int(pred.shape[1])
+    p = _device_tensor(pred.reshape(B, S, _flat(pred.shape[2:])), "pred")
+    g = _device_tensor(target.reshape(B, _flat(target.shape[1:])), "target")
+    n = int(n)
+    dev, L = p.device, _lib.lib()
+    idx = torch.empty(B, max(n, 0), device=dev, dtype=torch.int64)
+    score = torch.empty(B, max(n, 0), device=dev, dtype=torch.float32)
+    closest = torch.empty(B, device=dev, dtype=torch.int64) if from_closest else None
+    dist = torch.empty(B, S + 1, S + 1, device=dev, dtype=torch.float32) if want_dist else None
+    ws = torch.empty(max(int(L.sd_diverse_rank_workspace_bytes(B, S)), 1), device=dev, dtype=torch.uint8)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    check(L.sd_diverse_rank(p.data_ptr(), g.data_ptr(), B, S, p.shape[2], n, int(bool(from_closest)), idx.data_ptr(),
+                            score.data_ptr(), _lib.ptr(closest), _lib.ptr(dist), ws.data_ptr(), ws.numel(), stream))
+    return DiverseRank(idx, score, closest), dist
+
+
+def diverse_rank(pred: torch.Tensor, target: torch.Tensor, n: int, from_closest: bool = False) -> DiverseRank:
+    """Farthest-point greedy over each sequence's samples (ranking.py:3-40): pred (B, S, ...), target (B, ...)
+    -> DiverseRank.  Starting from the target (or, with from_closest, from the sample nearest to it,
+    ranking.py:42-63), each pick is the sample farthest from everything chosen so far, the lowest index on
+    a tie; a NaN sample is picked last (the reference raises).  Two launches on the current stream,
+    nothing is copied to the host.  S <= 255, 1 <= n <= S."""
+    return _rank(pred, target, n, from_closest)[0]
+
+
+def find_samples_maxapd_wrtGT(pred: torch.Tensor, target: torch.Tensor, num_chosen_samples: int = 5):
+    """ranking.py:30-40: (None, idx (B, num_chosen_samples) int64 on the device); `idx.tolist()` is the
+    reference's list of lists."""
+    return None, _rank(pred, target, num_chosen_samples, False)[0].idx
+
+
+def get_closest_and_nfurthest_maxapd(y_pred: torch.Tensor, y_gt: torch.Tensor, nsamples: int):
+    """ranking.py:42-63: y_pred (S, T, J, 3), y_gt (T, J, 3) -> (pred_closest (T, J, 3), sorted_preds
+    (nsamples, T, J, 3), idx (nsamples,) int64): the sample closest to the ground truth, then the nsamples
+    most mutually distant ones starting from it.  With a leading batch axis on both, every result has it
+    too.  The gathers are device ops; nothing is copied to the host."""
+    batched = y_pred.dim() == 5
+    assert y_pred.dim() in (4, 5) and y_pred.shape[-1] == 3, f"Expected SxTxJx3 tensors, got {y_pred.dim()}"
+    assert y_gt.dim() == y_pred.dim() - 1 and y_gt.shape[-2:] == y_pred.shape[-2:], f"Expected TxJx3 tensors, got {y_gt.dim()}"
+    p, g = (y_pred, y_gt) if batched else (y_pred.unsqueeze(0), y_gt.unsqueeze(0))
+    r = _rank(p, g, nsamples, True)[0]
+    rows = torch.arange(p.shape[0], device=r.idx.device)
+    pred_closest, sorted_preds = p[rows, r.closest], p[rows.unsqueeze(1), r.idx]
+    if batched:
+        return pred_closest, sorted_preds, r.idx
+    return pred_closest[0], sorted_preds[0], r.idx[0]
+
+
+# ---- class-wise CMD (sd_class_sum) and the metric storers (DESIGN.md §4aa) ---------------------------------------
+class CMDAccumulator:
+    """The reference's `CMDMetricStorer` + `resolve_cmd` (src/metrics/cmd.py:15-57) without the per-batch
+    host copies: float64 sums (C, W) of the motion profiles per class, int64 counts (C) and an int64 total
+    on `device`.  `mean_motion_per_class` holds the dataset's mean motion per class, in class-index order.
+    On a ROCm device `update` is one sd_class_sum launch; on the CPU (a state for `merge` / `all_reduce`,
+    or a host evaluation) the same row-ordered float64 sums are formed with torch ops."""
+
+    def __init__(self, mean_motion_per_class, device=None):
+        self.ref = [float(v) for v in mean_motion_per_class]
+        self.classes = len(self.ref)
+        if self.classes < 1:
+            raise ValueError("CMDAccumulator: mean_motion_per_class is empty")
+        self.device = torch.device(device or "cpu")
+        self.sum = None  # (C, W) once the first update gives W
+        self.count = torch.zeros(self.classes, dtype=torch.int64, device=self.device)
+        self.total = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def reset(self) -> None:
+        self.sum = None
+        self.count.zero_()
+        self.total.zero_()
+
+    def _state(self, width: int) -> torch.Tensor:
+        if self.sum is None:
+            self.sum = torch.zeros(self.classes, width, dtype=torch.float64, device=self.device)
+        elif self.sum.shape[1] != width:
+            raise ValueError(f"CMDAccumulator: profiles of {width} steps after profiles of {self.sum.shape[1]}")
+        return self.sum
+
+    def update(self, motion: torch.Tensor, class_idx) -> None:
+        """motion (B, W) the batch's `motion_for_cmd(pred)`, class_idx (B,) class indices (tensor, array or
+        list).  Nothing is copied to the host."""
+        m = torch.as_tensor(motion).detach()
+        if m.dim() != 2:
+            raise ValueError(f"CMDAccumulator: motion (B, W) expected, got {tuple(m.shape)}")
+        c = torch.as_tensor(class_idx).to(dtype=torch.int64).reshape(-1)
+        if c.numel() != m.shape[0]:
+            raise ValueError(f"CMDAccumulator: {c.numel()} class indices for {m.shape[0]} rows")
+        m = m.to(self.device, torch.float32).contiguous()
+        c = c.to(self.device).contiguous()
+        s = self._state(int(m.shape[1]))
+        if m.shape[0] == 0:
+            return
+        if self.device.type == "cuda":
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            check(_lib.lib().sd_class_sum(m.data_ptr(), c.data_ptr(), m.shape[0], m.shape[1], self.classes, s.data_ptr(),
+                                          self.count.data_ptr(), self.total.data_ptr(), stream))
+            return
+        md = m.to(torch.float64)
+        for r in range(m.shape[0]):  # the kernel's order: per class the rows ascending
+            k = int(c[r])
+            if 0 <= k < self.classes:
+                s[k] += md[r]
+                self.count[k] += 1
+        self.total += m.shape[0]
+
+    def merge(self, other: "CMDAccumulator") -> "CMDAccumulator":
+        if other.sum is not None:
+            self._state(int(other.sum.shape[1])).add_(other.sum.to(self.device))
+        self.count += other.count.to(self.device)
+        self.total += other.total.to(self.device)
+        return self
+
+    def all_reduce(self, group=None) -> "CMDAccumulator":
+        """Sum the states over the ranks; every rank must have seen a batch (the width is the state's)."""
+        import torch.distributed as dist
+
+        if self.sum is None:
+            raise SkelDiffError("CMDAccumulator.all_reduce: no update yet on this rank (the profile width is unknown)")
+        dist.all_reduce(self.sum, op=dist.ReduceOp.SUM, group=group)
+        ints = torch.cat([self.count, self.total])
+        dist.all_reduce(ints, op=dist.ReduceOp.SUM, group=group)
+        self.count.copy_(ints[:-1])
+        self.total.copy_(ints[-1:])
+        return self
+
+    def _host(self):
+        """(sums (C, W) f64, counts (C) f64, total) on the host: the one copy"""
+        if self.sum is None:
+            raise SkelDiffError("CMDAccumulator: needs at least one update before it can be computed")
+        flat = torch.cat([self.sum.reshape(-1), self.count.to(torch.float64), self.total.to(torch.float64)]).cpu()
+        C, W = self.sum.shape
+        return flat[:C * W].reshape(C, W), flat[C * W:C * W + C], float(flat[-1])
+
+    def motion_per_class(self) -> torch.Tensor:
+        """cmd.py:22-29: (C, W) float64 on the host, the mean profile per class, zeros for an empty class."""
+        s, n, _ = self._host()
+        return torch.where(n.unsqueeze(1) > 0, s / n.clamp_min(1.0).unsqueeze(1), torch.zeros_like(s))
+
+    def compute(self) -> float:
+        """cmd.py:24-31: sum over the non-empty classes of cmd(mean profile, class mean motion) * count /
+        total, in float64, as a Python float."""
+        s, n, total = self._host()
+        out = 0.0
+        for k in range(self.classes):
+            if n[k] > 0:
+                out += cmd(s[k] / n[k], self.ref[k]) * (float(n[k]) / total)
+        return out
+
+
+class MetricAccumulator:
+    """The reference's `MetricStorer` (src/metrics/metric_storer.py) with a float64 state on the device
+    of the values it is fed: return_op 'mean' / 'avg' (sum over the rows / number of rows), 'max', 'min'.
+    As the reference's (metric_storer.py:16), 'max' starts at 0 and 'min' at 1000000.  Torch ops only (not
+    a hot path); nothing is copied to the host before `compute`."""
+
+    def __init__(self, return_op="mean", device=None):
+        assert return_op in ["mean", "avg", "max", "min"]
+        self.return_op = return_op
+        self.device = torch.device(device) if device is not None else None
+        self.reset()
+
+    def _start(self) -> float:
+        return 1000000.0 if self.return_op == "min" else 0.0
+
+    def reset(self) -> None:
+        self.cumulator = None  # float64 () or (k,), on the first update's device
+        self.count = 0         # rows fed (host: shapes are known without a copy)
+
+    def _fold(self, v: torch.Tensor) -> None:
+        if self.cumulator is None:
+            self.cumulator = torch.full(v.shape, self._start(), dtype=torch.float64, device=v.device)
+        if self.return_op in ("mean", "avg"):
+            self.cumulator = self.cumulator + v
+        elif self.return_op == "max":
+            self.cumulator = torch.maximum(self.cumulator, v)
+        else:
+            self.cumulator = torch.minimum(self.cumulator, v)
+
+    def update(self, values: torch.Tensor) -> None:
+        """values (B,) or (B, k): one row per sequence."""
+        v = torch.as_tensor(values).detach()
+        if v.dim() not in (1, 2):
+            raise ValueError(f"MetricAccumulator: values (B,) or (B, k) expected, got {tuple(v.shape)}")
+        v = v.to(self.device if self.device is not None else v.device, torch.float64)
+        if self.device is None:
+            self.device = v.device
+        if v.shape[0] == 0:
+            return
+        if self.return_op in ("mean", "avg"):
+            self._fold(v.sum(0))
+            self.count += int(v.shape[0])
+        else:
+            self._fold(v.max(0).values if self.return_op == "max" else v.min(0).values)
+
+    def merge(self, other: "MetricAccumulator") -> "MetricAccumulator":
+        assert other.return_op == self.return_op
+        if other.cumulator is not None:
+            if self.device is None:
+                self.device = other.cumulator.device
+            self._fold(other.cumulator.to(self.device))
+        self.count += other.count
+        return self
+
+    def all_reduce(self, group=None) -> "MetricAccumulator":
+        """SUM (and the row count), MAX or MIN over the ranks."""
+        import torch.distributed as dist
+
+        if self.cumulator is None:
+            raise SkelDiffError("MetricAccumulator.all_reduce: no update yet on this rank (the value shape is unknown)")
+        if self.return_op in ("mean", "avg"):
+            both = torch.cat([self.cumulator.reshape(-1), torch.tensor([float(self.count)], dtype=torch.float64,
+                                                                       device=self.cumulator.device)])
+            dist.all_reduce(both, op=dist.ReduceOp.SUM, group=group)
+            self.cumulator = both[:-1].reshape(self.cumulator.shape)
+            self.count = int(both[-1])
+        else:
+            dist.all_reduce(self.cumulator, op=dist.ReduceOp.MAX if self.return_op == "max" else dist.ReduceOp.MIN,
+                            group=group)
+        return self
+
+    def compute(self):
+        """metric_storer.py:38-43: a Python float for (B,) values, a float64 host tensor (k,) for (B, k):
+        the one copy to the host."""
+        if self.cumulator is None:
+            raise SkelDiffError("MetricAccumulator must have at least one example before it can be computed.")
+        tot = self.cumulator.cpu()
+        if self.return_op in ("mean", "avg"):
+            tot = tot / self.count
+        return float(tot) if tot.dim() == 0 else tot
+
+
 __all__ = ["lat_apd", "apd", "ade", "fde", "mmade", "mmfde", "cmd", "mpjpe", "best_sample", "get_best_sample_idx",
            "choose_best_sample", "limb_stretching_normed_rmse", "limb_stretching_normed_mean", "limb_jitter_normed_rmse",
            "limb_jitter_normed_mean", "mae", "motion_for_cmd", "realism", "Realism", "FIDClassifier", "FIDAccumulator",
-           "frechet_distance", "APDEAccumulator"]
+           "frechet_distance", "APDEAccumulator", "diverse_rank", "DiverseRank", "find_samples_maxapd_wrtGT",
+           "get_closest_and_nfurthest_maxapd", "CMDAccumulator", "MetricAccumulator"]
