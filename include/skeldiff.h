@@ -216,7 +216,9 @@ int sd_profile_step(const sd_plan* plan, const float* x_t, const float* x_cond, 
  * sd_ade_fde: pred (nseq, samples, frames, features), target (nseq, frames, features) -> per
  *   sequence min over samples of the mean-over-frames L2 distance (ade, multimodal.py:44-57) and
  *   of the last frame's distance (fde, :60-73); per_sample_* (nseq, samples) receive the
- *   distances before the minimum (reduction != 'mean'); any output may be NULL. */
+ *   distances before the minimum (reduction != 'mean'); any output may be NULL.  The minimum is
+ *   torch.min's: NaN if one sample's distance is NaN (a diverged sample is reported, not skipped);
+ *   a +Inf distance loses to any number. */
 int sd_pairwise_distances(const float* x, int64_t nseq, int32_t samples, int64_t features, float* l1_mean,
                           float* l2_mean, void* stream);
 int sd_ade_fde(const float* pred, const float* target, int64_t nseq, int32_t samples, int32_t frames,
@@ -227,7 +229,8 @@ int sd_ade_fde(const float* pred, const float* target, int64_t nseq, int32_t sam
  * FDE against that ground truth (pair_ade / pair_fde, npairs each), then per sequence their
  * mean (mmade / mmfde, nseq; NaN for a sequence without ground truths, as the reference's
  * mean of an empty tensor).  pred (nseq, samples, frames, features).  seq_offsets and
- * pair_seq are device int64 arrays. */
+ * pair_seq are device int64 arrays.  The minimum over samples is sd_ade_fde's (NaN if one
+ * sample's distance is NaN), and a sequence's mean is NaN if one of its pairs is. */
 int sd_mm_ade_fde(const float* pred, const float* gts, const int64_t* pair_seq, int64_t npairs,
                   const int64_t* seq_offsets, int64_t nseq, int32_t samples, int32_t frames, int64_t features,
                   float* pair_ade, float* pair_fde, float* mmade, float* mmfde, void* stream);

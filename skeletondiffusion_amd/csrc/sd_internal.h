@@ -194,4 +194,19 @@ hipError_t launch_fold_gain(const float* W, const float* g, float mult, float* o
                             int64_t rows, int K, hipStream_t s);
 hipError_t launch_sigma(const float* logvar, float* sig, int64_t n, hipStream_t s);
 
+// The minimum over a sequence's samples in the metric kernels (sd_metrics.hip k_ade_fde, sd_realism.hip
+// k_realism_reduce): the smallest of v[0..S) as torch.min, NaN if there is one
+__device__ __forceinline__ float min_or_nan(const float* v, int S) {
+    float m = v[0];
+    for (int s = 1; s < S; ++s) {
+        const float x = v[s];
+        if (x != x || m != m) {
+            m = __builtin_nanf("");
+        } else if (x < m) {
+            m = x;
+        }
+    }
+    return m;
+}
+
 }  // namespace sd

@@ -8,6 +8,9 @@
 //   mmade / mmfde: the same minimum against each of a sequence's multimodal ground truths,
 //             averaged over them (multimodal.py:108-135): one workgroup per (sequence, gt) pair,
 //             then a fixed-order mean per sequence.
+//             Non-finite values go where torch takes them: the minimum over samples is torch.min's, NaN
+//             as soon as one sample's distance is NaN (min_or_nan, sd_internal.h; a +Inf distance loses
+//             to any number), and the means over pairs and over ground truths propagate NaN.
 //   best sample: per (sequence, sample) the mean per-joint L2 distance to the target (mpjpe,
 //             multimodal.py:37-42), one workgroup per pair; then per sequence the first minimum and
 //             the gather of that sample (metrics/utils.py:12-30) -- see k_sample_dist below.
@@ -110,7 +113,7 @@ __global__ __launch_bounds__(256) void k_ade_fde(const float* __restrict__ pred,
                                                  float* __restrict__ fde, float* __restrict__ per_sample_ade,
                                                  float* __restrict__ per_sample_fde,
                                                  const int64_t* __restrict__ pair_seq) {
-    __shared__ float sum_t[kMaxSamples], last_t[kMaxSamples];
+    __shared__ float mean_t[kMaxSamples], last_t[kMaxSamples];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t seq = pair_seq ? pair_seq[blockIdx.x] : (int64_t)blockIdx.x;
     const float* ps = pred + seq * S * T * F;
@@ -129,24 +132,18 @@ __global__ __launch_bounds__(256) void k_ade_fde(const float* __restrict__ pred,
             if (t == T - 1) last = dn;
         }
         if (lane == 0) {
-            sum_t[s] = acc_t;
+            mean_t[s] = acc_t / T;
             last_t[s] = last;
         }
     }
     __syncthreads();
     if (per_sample_ade)
-        for (int s = tid; s < S; s += 256) per_sample_ade[(int64_t)blockIdx.x * S + s] = sum_t[s] / T;
+        for (int s = tid; s < S; s += 256) per_sample_ade[(int64_t)blockIdx.x * S + s] = mean_t[s];
     if (per_sample_fde)
         for (int s = tid; s < S; s += 256) per_sample_fde[(int64_t)blockIdx.x * S + s] = last_t[s];
-    if (tid == 0) {
-        float best = INFINITY, bestf = INFINITY;
-        for (int s = 0; s < S; ++s) {
-            best = fminf(best, sum_t[s] / T);
-            bestf = fminf(bestf, last_t[s]);
-        }
-        if (ade) ade[blockIdx.x] = best;
-        if (fde) fde[blockIdx.x] = bestf;
-    }
+    // the reference's dist.min(axis=-1).values (multimodal.py:55, :71, :117, :133): a NaN sample makes the minimum NaN
+    if (ade && tid == 0) ade[blockIdx.x] = min_or_nan(mean_t, S);
+    if (fde && tid == 64) fde[blockIdx.x] = min_or_nan(last_t, S);
 }
 
 // per sequence the mean of its pairs' values in pair order (offsets: nseq + 1); 0 pairs -> NaN

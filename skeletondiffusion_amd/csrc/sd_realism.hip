@@ -249,20 +249,7 @@ __global__ __launch_bounds__(kThreads) void k_realism_pred(
 }
 
 // ---- per sequence: means over (S, L), minimum over samples, motion profile ----------------------------
-// the smallest of v[0..S) as torch.min: NaN if there is one
-__device__ __forceinline__ float min_or_nan(const float* v, int S) {
-    float m = v[0];
-    for (int s = 1; s < S; ++s) {
-        const float x = v[s];
-        if (x != x || m != m) {
-            m = __builtin_nanf("");
-        } else if (x < m) {
-            m = x;
-        }
-    }
-    return m;
-}
-
+// (the minimum over samples: min_or_nan, sd_internal.h)
 __global__ __launch_bounds__(kThreads) void k_realism_reduce(int64_t B, int S, int T, int L,
                                                              const double* __restrict__ limb_scratch,
                                                              float* __restrict__ mean_out,

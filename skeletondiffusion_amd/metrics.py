@@ -115,7 +115,8 @@ def _ade_fde(target, pred, t0, t, reduction, want_ade):
 def ade(target: torch.Tensor, pred: torch.Tensor, t0: int = 0, t: int = -1, reduction: str = "mean", **kwargs):
     """target (batch, seq_length, ...), pred (batch, num_samples, seq_length, ...): min over samples
     of the mean over frames of the L2 distance (reduction 'mean'), else the (batch, num_samples)
-    distances."""
+    distances.  The minimum is torch.min's, as the reference's `dist.min(axis=-1).values`: a sample
+    with a NaN makes its sequence's value NaN; a sample with an Inf distance is passed over."""
     return _ade_fde(target, pred, t0, t, reduction, True)
 
 
@@ -158,7 +159,8 @@ def mmade(target: torch.Tensor, pred: torch.Tensor, mm_gt, t0: int = 0, t: int =
     """Multimodal ADE (multimodal.py:108-120): pred (batch, num_samples, seq_length, ...), mm_gt a
     sequence of batch tensors (n_gts_i, seq_length, ...): per sequence the mean over its ground
     truths of the min over samples of the mean-over-frames L2 distance (RuntimeError for a
-    sequence without ground truths, as the reference).  `target` is unused, as in the reference."""
+    sequence without ground truths, as the reference).  `target` is unused, as in the reference.
+    As in ade, a sample with a NaN makes every minimum of its sequence, and so the sequence's mean, NaN."""
     return _mm(target, pred, mm_gt, t0, t, True)
 
 
