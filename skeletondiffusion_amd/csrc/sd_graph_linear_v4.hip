@@ -32,6 +32,7 @@
 #include "sd_gl4_args.h"
 #include "sd_gl4_lds.h"
 #include "sd_internal.h"
+#include "sd_store_policy.h"
 #include "sd_ystore_map.h"
 
 namespace sd {
@@ -56,6 +57,10 @@ struct VmCnt4 {
 };
 
 __device__ __forceinline__ floatx4 g4(const float* p) { return *reinterpret_cast<const floatx4*>(p); }
+
+// a compile-time index as a lambda argument (a store's piece: its offset is the instruction's immediate)
+template <int V>
+using Idx = std::integral_constant<int, V>;
 
 // tanh(x) = 1 - 2 / (exp(2x) + 1) on v_exp_f32 + v_rcp_f32 (no IEEE division sequence):
 // saturates cleanly at +-1, within ~3e-7 absolute of tanhf
@@ -400,22 +405,31 @@ __global__ __launch_bounds__(256) void k_gl4y(const GL4GArgs p) {
         if (ROWMAJOR && arow >= p.B) return;  // row-major z holds rows < B only
         float* y = p.y + tr * p.y_ts + (int64_t)j * p.y_js + (int64_t)tc * p.y_cs +
                    (ROWMAJOR ? ystore_rm_piece_off(l32, h, 0, p.y_rs) : ystore_zs_piece_off(l32, h, 0));
+        // the tile's four bias pieces before its stores (sd_store_policy.h: no LDS read moves across one)
+        floatx4 bq[4];
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const floatx4 b4 = *reinterpret_cast<const floatx4*>(sB + ystore_col(g, h));
+        for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const floatx4*>(sB + ystore_col(g, h));
+        auto piece = [&](auto gc) {  // (g a constant: the scratch piece's offset is the store's immediate)
+            constexpr int g = decltype(gc)::value;
+            const floatx4 b4 = bq[g];
             floatx4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = v[4 * g + e] * sc + b4[e];
             const int col = tc * 32 + ystore_col(g, h);
             if (vec) {  // N % 4 == 0: a piece is inside or outside as a whole (the scratch: N % 32 == 0)
-                if (!ROWMAJOR) *reinterpret_cast<floatx4*>(y + ystore_zs_piece_off(0, 0, g)) = o;
+                // the scratch: one contiguous KiB per instruction, written through (sd_store_policy.h)
+                if (!ROWMAJOR) store16<kStoreGemmY, 4 * ystore_zs_piece_off(0, 0, g)>(y, o);
                 else if (col < p.N) *reinterpret_cast<floatx4*>(y + ystore_col(g, 0)) = o;
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (col + e < p.N) y[ystore_col(g, 0) + e] = o[e];
             }
-        }
+        };
+        piece(Idx<0>{});
+        piece(Idx<1>{});
+        piece(Idx<2>{});
+        piece(Idx<3>{});
     };
     store(acc);
     // f16 range left: the tile again on exact-f32 MFMA (operands swapped: the same lane layout), stored
@@ -743,16 +757,26 @@ __device__ __forceinline__ void gl4t_body(const GL4GArgs& p, const Unit3 un, con
             sc *= 1.0f / fmaxf(sqrtf(t), 1e-12f);
         }
         float* y = p.y + tr * p.y_ts + (int64_t)j * p.y_js + (int64_t)cg * CT * p.y_cs + (ROWMAJOR ? 0 : ystore_zs_piece_off(l32, h, 0));
-        auto store_tile = [&](int ct, const floatx16& v) {
+        // a tile's four bias pieces, read one tile ahead of its stores (sd_store_policy.h: no LDS read moves across one)
+        auto load_bias = [&](int ct, floatx4 (&bq)[4]) {
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const floatx4 bv = sBr[(ct * 32 + ystore_col(g, 0)) / 4];
+            for (int g = 0; g < 4; ++g) bq[g] = sBr[(ct * 32 + ystore_col(g, 0)) / 4];
+        };
+        auto store_tile = [&](int ct, const floatx16& v, const floatx4 (&bq)[4]) {
+            auto piece = [&](auto gc) {  // (g a constant: the scratch piece's offset is the store's immediate)
+                constexpr int g = decltype(gc)::value;
+                const floatx4 bv = bq[g];
                 floatx4 o;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) o[e] = v[4 * g + e] * sc + bv[e];
                 if constexpr (ROWMAJOR) *reinterpret_cast<floatx4*>(sT + l32 * TS + ystore_col(g, h)) = o;
-                else *reinterpret_cast<floatx4*>(y + (int64_t)ct * p.y_cs + ystore_zs_piece_off(0, 0, g)) = o;
-            }
+                // the scratch: one contiguous KiB per instruction, written through (sd_store_policy.h)
+                else store16<kStoreGemmY, 4 * ystore_zs_piece_off(0, 0, g)>(y + (int64_t)ct * p.y_cs, o);
+            };
+            piece(Idx<0>{});
+            piece(Idx<1>{});
+            piece(Idx<2>{});
+            piece(Idx<3>{});
             if constexpr (ROWMAJOR) {
                 __builtin_amdgcn_wave_barrier();  // DS operations of one wave complete in order
 #pragma unroll
@@ -765,8 +789,13 @@ __device__ __forceinline__ void gl4t_body(const GL4GArgs& p, const Unit3 un, con
                 __builtin_amdgcn_wave_barrier();
             }
         };
+        floatx4 bq[2][4];
+        load_bias(0, bq[0]);
 #pragma unroll
-        for (int ct = 0; ct < CT; ++ct) store_tile(ct, acc[rt][ct]);
+        for (int ct = 0; ct < CT; ++ct) {
+            if (ct + 1 < CT) load_bias(ct + 1, bq[(ct + 1) & 1]);
+            store_tile(ct, acc[rt][ct], bq[ct & 1]);
+        }
         // f16 range left: every tile of the row tile again on exact-f32 MFMA (operands swapped: the
         // same lane layout), stored over the first (same lanes, same addresses: program order) --
         // after the stores
@@ -780,7 +809,8 @@ __device__ __forceinline__ void gl4t_body(const GL4GArgs& p, const Unit3 un, con
                                                               p.K2, p.x2_blk, p.B, p.J, second ? p.W2 : p.W,
                                                               jt * (p.pair_n ? p.pair_n : p.N), p.pair_n ? p.pair_n : p.N,
                                                               unscale, row0[rt], j, second ? col - p.pair_n : col);
-                store_tile(ct, ex);
+                load_bias(ct, bq[0]);
+                store_tile(ct, ex, bq[0]);
             }
         }
     }

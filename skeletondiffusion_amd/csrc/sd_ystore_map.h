@@ -25,11 +25,11 @@
 namespace sd {
 
 // first column (of the tile's 32) of the 16-B piece that lane half h stores with store g
-SD_YS_HD int ystore_col(int g, int h) { return 8 * g + 4 * h; }
+SD_YS_HD constexpr int ystore_col(int g, int h) { return 8 * g + 4 * h; }
 
 // float offset of that piece for the lane's row l32 ...
 // ... inside a 4-KiB scratch block
-SD_YS_HD int ystore_zs_piece_off(int l32, int h, int g) { return g * 256 + l32 * 8 + 4 * h; }
+SD_YS_HD constexpr int ystore_zs_piece_off(int l32, int h, int g) { return g * 256 + l32 * 8 + 4 * h; }
 // ... inside a row-major tile with row stride y_rs (the J > 21 path's z)
 SD_YS_HD int64_t ystore_rm_piece_off(int l32, int h, int g, int64_t y_rs) { return (int64_t)l32 * y_rs + ystore_col(g, h); }
 
