@@ -445,10 +445,11 @@ int sd_test_qkv_attention(const float* x, int32_t K, const float* W, const int64
                           void* stream);
 /* Test hook: the kernel generation of the sd_test_* entry points ONLY (plans never read it; a
  * plan's generation is its SD_OPT_KERNEL_VARIANT / SD_OPT_GL4_TILE):
- * gl_variant 0 = auto (v4 split-f16 where available, else exact-f32 v3/v2/v5), 1..3 = exact-f32
- * generations, 4 = v4, 5 = v5; gl4_tile = <waves><row tiles><col tiles> (e.g. 822) or 0 = auto,
- * -1 leaves it.  Returns the previous gl_variant, or -1 for an invalid one (nothing changed);
- * gl_variant = -1 only queries (returns the current value). */
+ * gl_variant 0 = auto (v4 split-f16 where available, else exact-f32 v3/v2/v5), 2 / 3 = exact-f32
+ * generations (1, the removed first generation, runs 2), 4 = v4, 5 = v5; gl4_tile =
+ * <waves><row tiles><col tiles> (e.g. 822) or 0 = auto, -1 leaves it.  Returns the previous
+ * gl_variant, or -1 for an invalid one (nothing changed); gl_variant = -1 only queries (returns
+ * the current value). */
 int sd_test_set_kernel_variant(int32_t gl_variant, int32_t gl4_tile);
 /* Test hook: the v4 split route of the sd_test_graph_linear* entry points ONLY (as
  * SD_OPT_SPLIT_ROUTE: 0 auto, 1 never, 2 k_gl4y GEMM phase, 3 k_gl4t GEMM phase, 4 k_gl4t except
@@ -461,7 +462,8 @@ int sd_test_set_split_route(int32_t route);
  * environment read at library load and keeps its own options, so two plans may hold different
  * options and sample concurrently.  SD_E_INVALID for an unknown option or value. */
 enum {
-    SD_OPT_KERNEL_VARIANT = 1,  /* 0 auto, 1..5 force a graph-linear generation */
+    SD_OPT_KERNEL_VARIANT = 1,  /* 0 auto, 2..5 force a graph-linear generation; 1 (the removed
+                                   first generation) is an alias of 2 */
     SD_OPT_GL4_TILE = 2,        /* v4 tile <waves><row tiles><col tiles>, 0 = per shape */
     SD_OPT_ROW_CHAINS = 3,      /* 1..8 concurrent row chains in sd_sample_loop; 0 = auto
                                    (3, or 2 at <= 1,200 rows) */

@@ -22,13 +22,13 @@
 #include <string>
 
 #include "../../include/skeldiff.h"
+#include "sd_device.h"
 #include "sd_internal.h"
 
 namespace sd {
 namespace {
 
 constexpr int KF = 16;  // padded width of the frame features (F <= 16)
-constexpr size_t kGateLdsMax = 160 * 1024;  // k_gru_gate's dynamic LDS (gl3_launch / gl2_launch use the same limit)
 
 // gx table: row i of gx_t for t = 0 .. ph-1 (rows are independent under the row-L1 normalize)
 __global__ void k_gx_table(const float* __restrict__ G, const float* __restrict__ Gadd, int J, int ph,
@@ -209,11 +209,11 @@ int check_desc(const sd_gru_decoder_desc* d) {
     // k_gru_gate keeps a row's x_res (J, 3H) and gx_t (J, J) in dynamic LDS: refuse what cannot fit
     // (160 KiB, the limit of the graph-linear launches) here, not mid-sequence as an SD_E_HIP
     const size_t gate_lds = ((size_t)d->num_nodes * 3 * d->hidden_size + (size_t)d->num_nodes * d->num_nodes) * sizeof(float);
-    if (gate_lds > sd::kGateLdsMax)
+    if (gate_lds > sd::kLdsMax)
         return dfail(SD_E_INVALID, "num_nodes = " + std::to_string(d->num_nodes) + " with hidden_size = " +
                                        std::to_string(d->hidden_size) + " needs " + std::to_string(gate_lds) +
                                        " bytes of gate LDS (3 num_nodes hidden_size + num_nodes^2 floats), over the " +
-                                       std::to_string(sd::kGateLdsMax) + " available");
+                                       std::to_string(sd::kLdsMax) + " available");
     return SD_OK;
 }
 }  // namespace
@@ -268,8 +268,7 @@ int sd_gru_decode(const sd_gru_decoder_desc* d, const float* x, const float* h, 
     DHIP(sd::launch_graph_linear(sd::gl(d, w.xprev, sd::KF, h, L, w.winit, d->init_bias, w.ghat_init, H, w.h0, JH, rows, 0), false, s));
     DHIP(sd::launch_graph_linear(sd::gl(d, w.xlast, sd::KF, h, L, w.wih, d->bias_ih, w.ident, 3 * H, w.xres, JH3, rows, 0), false, s));
     size_t gate_lds = ((size_t)J * 3 * H + (size_t)J * J) * sizeof(float);
-    if (gate_lds > 64 * 1024)
-        DHIP(hipFuncSetAttribute((const void*)sd::k_gru_gate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gate_lds));
+    DHIP(sd::lds_opt_in(sd::k_gru_gate, gate_lds));
     float* hx = w.h0;
     float* hn = w.h1;
     for (int t = 0; t < ph; ++t) {
@@ -334,8 +333,7 @@ int sd_gru_encode(const sd_gru_decoder_desc* d, const float* x, int64_t rows, in
     DHIP(sd::launch_ghat(d->fc_G, w.ghat_fc, J, 1, s));
     const int64_t JH = (int64_t)J * H, JH3 = 3 * JH;
     size_t gate_lds = ((size_t)J * 3 * H + (size_t)J * J) * sizeof(float);
-    if (gate_lds > 64 * 1024)
-        DHIP(hipFuncSetAttribute((const void*)sd::k_gru_gate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gate_lds));
+    DHIP(sd::lds_opt_in(sd::k_gru_gate, gate_lds));
     // x (rows, frames, J, F): frame t -> xprev via k_pad_frame's (rows, 2, J, F) view at stride
     // frames: done with a strided copy kernel of its own
     hipLaunchKernelGGL(sd::k_pad_frame_t, grid(rows * J * sd::KF), dim3(256), 0, s, x, rows, frames, J, F, 0, w.xprev);

@@ -27,14 +27,12 @@
 #include <string>
 
 #include "../../include/skeldiff.h"
+#include "sd_device.h"
 #include "sd_internal.h"
 
 namespace sd {
 
 namespace {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int kH = 128;        // hidden size (the only one)
 // 32-row MFMA tiles per workgroup.  The product is 1; -DSD_FID_ROW_TILES=2 builds the 64-row variant of the
@@ -384,7 +382,7 @@ int sd_fid_features(const sd_fid_classifier_desc* desc, const float* motion, int
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail("k_fid_pack", e);
     const size_t lds = (size_t)kRT * (2 * pk.g0 * kFrag + 4 * kGH * kFrag) * sizeof(float);  // <= 80 KiB per row tile
-    e = hipFuncSetAttribute((const void*)k_fid_features, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    e = lds_opt_in(k_fid_features, lds);
     if (e != hipSuccess) return hip_fail("k_fid_features (LDS size)", e);
     const int64_t tiles = (rows + kTile - 1) / kTile;
     hipLaunchKernelGGL(k_fid_features, dim3((unsigned)tiles), dim3(kThreads), lds, s, motion, rows, frames,

@@ -56,9 +56,10 @@ SD_HD Unit3 decode_unit(uint32_t u, FastDiv a, FastDiv b) {
     return r;
 }
 
-// XCD-aware order of k_gl4t (and the one-kernel k_gl4): workgroups b, b + 8, ... run on one XCD and
-// take a contiguous share of the units, so the column groups of one (row group, node) -- which read
-// the same x -- meet in one L2.  q8 = grid / 8, r8 = grid % 8: the first r8 XCDs take q8 + 1 units.
+// XCD-aware order (cdna_hip_programming.md §5.5 T1) of k_gl4t, the one-kernel k_gl4, k_gl3 and k_gl2:
+// workgroups b, b + 8, ... run on one XCD and take a contiguous share of the units, so the column groups
+// of one (row group, node) -- which read the same x -- meet in one L2.  q8 = grid / 8, r8 = grid % 8: the
+// first r8 XCDs take q8 + 1 units.  Bijective for any grid size.
 SD_HD uint32_t xcd_remap(uint32_t block, uint32_t q8, uint32_t r8) {
     const uint32_t xcd = block & 7;
     return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (block >> 3);

@@ -21,9 +21,6 @@
 
 namespace sd {
 
-constexpr size_t kGl4LdsDefault = 64 * 1024;  // dynamic LDS a launch may take without the attribute call
-constexpr size_t kGl4LdsMax = 160 * 1024;     // of a CU: a larger tile is refused
-
 struct Gl4Lds {
     int COLS;          // 32 CT
     int YR, YS;        // MODE 0 / 2: floats per Y row, per node of a 16-row slab

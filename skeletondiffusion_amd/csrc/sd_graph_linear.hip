@@ -1,12 +1,18 @@
-// k_gl2: StaticGraphLinear (graph_structural.py:30-43) + fused epilogue, v2 schedule for gfx950.
+// StaticGraphLinear (graph_structural.py:30-43) + fused epilogue: the dispatcher over the kernel
+// generations (launch_graph_linear, at the end) and k_gl2, the v2 schedule for gfx950 -- the exact-f32
+// kernel every other generation falls through to.
 //
-// Same math and register tile as v1 (sd_kernels.hip, k_graph_linear): a wave owns 16 rows x
-// (16*NCB) output columns for ALL J nodes, the exact-f32 MFMA v_mfma_f32_16x16x4_f32 does the
-// per-node GEMM, and the G-hat node mixing + epilogue run in registers.  What changes is how the
-// operands arrive:
+// k_gl2's tile.  Workgroup = 4 waves; a wave owns 16 rows x (16*NCB) output columns for ALL J nodes,
+// so the G-hat node mixing (which couples the J nodes of a row) and the epilogue run in registers.
+// The per-node GEMM is on the exact-f32 MFMA v_mfma_f32_16x16x4_f32, operand maps
+// (cdna_hip_programming.md §3): lane l supplies A[l&15][k=l>>4] and B[k=l>>4][l&15];
+// D[row=4*(l>>4)+r][col=l&15].  k is permuted inside a 16-wide chunk so each lane reads ONE float4 of
+// x and ONE float4 of W per 4 MFMAs: in step s of chunk kc, position p = l>>4 carries k = kc + 4p + s
+// for both operands.
+// How the operands arrive:
 //   * the weight tile of a 16-deep k chunk (all node types x 16*NCB columns) is brought into LDS
 //     ONCE per workgroup by LDS-DMA (global_load_lds_dwordx4, no VGPRs), double-buffered, and
-//     shared by the 4 waves (v1 re-read it from L1/L2 in every wave);
+//     shared by the 4 waves;
 //   * LDS image [type][k-group][n][4 floats]: the 16 lanes of every ds_read_b128 lane group
 //     read 16 distinct consecutive 16-B slots -> conflict-free;
 //   * each node's x fragment for chunk c+1 is issued right after its last use in chunk c, so the
@@ -17,29 +23,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sd_device.h"
+#include "sd_gl4_args.h"
 #include "sd_internal.h"
 
 namespace sd {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
+thread_local unsigned g_route_bits = 0;
 
 namespace {
-
-__device__ __forceinline__ floatx4 gld4(const float* p) { return *reinterpret_cast<const floatx4*>(p); }
-
-__device__ __forceinline__ floatx4 mfma4(float a, float b, floatx4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-// s_waitcnt immediate for "vmcnt <= n" with lgkmcnt / expcnt untouched (gfx9 encoding:
-// vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt_hi[15:14])
-template <int N>
-struct VmCnt {
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    static constexpr int imm = (N & 0xF) | (0x7 << 4) | (0xF << 8) | ((N >> 4) << 14);
-};
 
 template <int NT>
 __device__ __forceinline__ void fill_w_stage(const GLArgs& p, int c0, int k0, int K, float* dst, int wave,
@@ -69,12 +61,10 @@ __global__ __launch_bounds__(256, MINW) void k_gl2(const GLArgs p) {
     float* sW1 = smem + stage;
     float* sG = smem + 2 * stage;
 
-    // XCD-aware tile order (cdna_hip_programming.md §5.5 T1): blocks b and b+8 share an XCD, so
-    // logical tile L = (blocks of this XCD, in order) keeps the column tiles of one row tile -
-    // which re-read the same x rows - inside one XCD's L2.  Bijective for any grid size.
+    // XCD-aware tile order: the column tiles of one row tile, which re-read the same x rows, stay
+    // inside one XCD's L2
     const int ntile_c = (p.N + NT - 1) / NT;
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
+    const int L = (int)xcd_remap(blockIdx.x, gridDim.x >> 3, gridDim.x & 7);
     const int ct = L % ntile_c;
     const int64_t rt = L / ntile_c;
     const int64_t row0 = rt * 64 + wave * 16;
@@ -92,7 +82,7 @@ __global__ __launch_bounds__(256, MINW) void k_gl2(const GLArgs p) {
     auto load_a = [&](int c, int j) -> floatx4 {
         const int k0 = c << 4;
         const float* src = (k0 < p.K1) ? x1r + (int64_t)j * p.K1 + k0 : x2r + (int64_t)j * p.K2 + (k0 - p.K1);
-        return gld4(src);
+        return ld4(src);
     };
 
     floatx4 acc[JM][NCB];
@@ -247,12 +237,9 @@ static hipError_t gl2_launch(const GLArgs& a, bool rms, hipStream_t s) {
     const int64_t ntile_r = (a.B + 63) / 64;
     const dim3 grid((unsigned)(ntile_c * ntile_r));
     size_t lds = (size_t)(2 * a.ntypes * NT * 16 + a.J * a.J) * sizeof(float);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > kLdsMax) return hipErrorInvalidValue;
     auto kt = rms ? k_gl2<JM, EXACT, NCB, true, PREF, MINW> : k_gl2<JM, EXACT, NCB, false, PREF, MINW>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (const hipError_t e = lds_opt_in(kt, lds); e != hipSuccess) return e;
     g_route_bits |= kRouteExact;
     hipLaunchKernelGGL(kt, grid, dim3(256), lds, s, a);
     return hipGetLastError();
@@ -280,6 +267,41 @@ hipError_t launch_graph_linear_v2(const GLArgs& a, bool rms, hipStream_t s) {
     if (a.J <= 16) return gl2_launch<16, false, 1, true, 2>(a, rms, s);
     if (a.J <= 32) return gl2_launch<32, false, 1, false, 2>(a, rms, s);
     return gl2_launch<64, false, 1, false, 1>(a, rms, s);
+}
+
+// 0 (default): v4 (f32-accurate split-f16 MFMA) where the plan prepared split weights and the
+// skeleton has an instantiation; otherwise the exact-f32 kernels per shape: v3 (node-split
+// waves, 32x32 f32 MFMA) for N < 512, where it measured 1.15-1.25x faster than v2; v2 with
+// 32-column tiles for the wide to_qkv layer (N = 768); v5 (node-batched GEMM + mixing pass) for
+// J > 21, where every one-kernel tile must stage all node types' weights.  2..5 force one
+// generation (falling through to v2 where the forced one does not apply); 1, the removed first
+// generation, is an alias of 2.
+hipError_t launch_graph_linear(const GLArgs& a, bool rms, hipStream_t s) {
+    const int v = a.variant;
+    // every generation computes a column tile from the whole K extent of its rows: an input that
+    // aliases the output would be overwritten by sibling column tiles while still being read
+    if (a.B > 0 && (a.x1 == a.out || (a.x2 && a.x2 == a.out))) return hipErrorInvalidValue;
+    if (a.skip_mix) return (v == 0 || v == 5) && a.J > 21 && a.prec != 2 ? launch_graph_linear_v5(a, rms, s) : hipErrorNotSupported;
+    // Block.norm 'layer' lives in the v4 mixing epilogue only (J = 16 / 17 / 21; plan-time checked)
+    if (a.ln_w) return v == 0 || v == 4 ? launch_graph_linear_v4(a, rms, s) : hipErrorNotSupported;
+    if (v == 4 || v == 0) {
+        const hipError_t e = launch_graph_linear_v4(a, rms, s);
+        if (e != hipErrorNotSupported) return e;
+    }
+    // bf16 operands (precision mode 2) exist only in the v4 tiles: no exact-f32 fallback
+    if (a.prec == 2 || a.x1_bf16 || a.x2_bf16 || a.res_bf16 || a.out_bf16) return hipErrorNotSupported;
+    // the exact-f32 generations read and write row-major activations only
+    if (a.x1_blk || a.x2_blk || a.res_blk || a.out_blk) return hipErrorNotSupported;
+    // large skeletons (J > 21, MANO J = 51: 43 node types): node-batched GEMM + mixing pass
+    if (v == 5 || (v == 0 && a.J > 21)) {
+        const hipError_t e = launch_graph_linear_v5(a, rms, s);
+        if (e != hipErrorNotSupported) return e;
+    }
+    if (v == 3 || (v == 0 && a.N < 512)) {
+        const hipError_t e = launch_graph_linear_v3(a, rms, s);
+        if (e != hipErrorNotSupported) return e;
+    }
+    return launch_graph_linear_v2(a, rms, s);
 }
 
 }  // namespace sd

@@ -19,25 +19,13 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "sd_device.h"
+#include "sd_gl4_args.h"
 #include "sd_internal.h"
 
 namespace sd {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
 namespace {
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ floatx4 g4(const float* p) { return *reinterpret_cast<const floatx4*>(p); }
-__device__ __forceinline__ floatx4 l4(const float* p) { return *reinterpret_cast<const floatx4*>(p); }
-
-template <int N>
-struct VmCnt3 {
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    static constexpr int imm = (N & 0xF) | (0x7 << 4) | (0xF << 8) | ((N >> 4) << 14);
-};
 
 // tanh(x) = 1 - 2 / (exp(2x) + 1): v_exp_f32 + v_rcp_f32; saturates cleanly at +-1 and is
 // within ~2e-7 absolute of tanhf (the layer outputs feed a 1e-4 end-to-end bar)
@@ -80,8 +68,7 @@ __global__ __launch_bounds__(256, 2) void k_gl3(const GLArgs p) {
     float* sG = smem + (wbytes > ybytes ? wbytes : ybytes);
 
     const int ntile_c = (p.N + 31) >> 5;
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
+    const int L = (int)xcd_remap(blockIdx.x, gridDim.x >> 3, gridDim.x & 7);
     const int ct = L % ntile_c;
     const int64_t row0 = (int64_t)(L / ntile_c) * 32;
     const int c0 = ct * 32;
@@ -107,8 +94,8 @@ __global__ __launch_bounds__(256, 2) void k_gl3(const GLArgs p) {
         const int j = min(node_of(m), J - 1);
         const int k0 = c << 4;
         const float* src = (k0 < p.K1) ? x1r + (int64_t)j * p.K1 + k0 : x2r + (int64_t)j * p.K2 + (k0 - p.K1);
-        lo = g4(src);
-        hi = g4(src + 4);
+        lo = ld4(src);
+        hi = ld4(src + 4);
     };
 
     fill_w3(p, c0, 0, K, sW0, wave, lane);
@@ -123,15 +110,15 @@ __global__ __launch_bounds__(256, 2) void k_gl3(const GLArgs p) {
         const int cn = min(c + 1, nchunk - 1);
         const bool rms_chunk = RMS && (c << 4) < p.K1;
         auto wfrag = [&](int m) { return cur + (((p.ntype[min(node_of(m), J - 1)] * 2 + h) * 2) * 32 + l32) * 4; };
-        floatx4 wa_n = l4(wfrag(0)), wb_n = l4(wfrag(0) + 128);  // weight fragments read one node ahead
+        floatx4 wa_n = ld4(wfrag(0)), wb_n = ld4(wfrag(0) + 128);  // weight fragments read one node ahead
 #pragma unroll
         for (int m = 0; m < NPW; ++m) {
             const int j = node_of(m);
             const floatx4 xa = a0[m], xb = a1[m];
             const floatx4 wa = wa_n, wb = wb_n;
             if (m + 1 < NPW) {
-                wa_n = l4(wfrag(m + 1));
-                wb_n = l4(wfrag(m + 1) + 128);
+                wa_n = ld4(wfrag(m + 1));
+                wb_n = ld4(wfrag(m + 1) + 128);
             }
             load_x(cn, m, a0[m], a1[m]);  // every wave issues exactly 2*NPW loads (vmcnt below)
             if (j >= J) continue;         // wave-uniform: only the MFMAs are skipped
@@ -151,7 +138,7 @@ __global__ __launch_bounds__(256, 2) void k_gl3(const GLArgs p) {
         }
         if (c + 1 < nchunk) {
             // this chunk issued: weight DMA for c+1, then 2*NPW x prefetches -> retire the DMA only
-            __builtin_amdgcn_s_waitcnt(VmCnt3<2 * NPW>::imm);
+            __builtin_amdgcn_s_waitcnt(VmCnt<2 * NPW>::imm);
             __builtin_amdgcn_s_barrier();
         }
     }
@@ -244,7 +231,7 @@ __global__ __launch_bounds__(256, 2) void k_gl3(const GLArgs p) {
             for (int ib = 0; ib < IB; ++ib) {
                 floatx4 z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int s = 0; s < KS; ++s) z = __builtin_amdgcn_mfma_f32_16x16x4f32(ga[ib][s], yb[s], z, 0, 0, 0);
+                for (int s = 0; s < KS; ++s) z = mfma4(ga[ib][s], yb[s], z);
                 if (!ok) continue;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -268,12 +255,9 @@ static hipError_t gl3_launch(const GLArgs& a, bool rms, hipStream_t s) {
     const dim3 grid((unsigned)(ntile_c * ntile_r));
     const size_t wfl = (size_t)2 * a.ntypes * 512, yfl = (size_t)J * YSTRIDE;
     size_t lds = ((wfl > yfl ? wfl : yfl) + (size_t)J * J) * sizeof(float);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > kLdsMax) return hipErrorInvalidValue;
     auto kt = rms ? k_gl3<J, true> : k_gl3<J, false>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (const hipError_t e = lds_opt_in(kt, lds); e != hipSuccess) return e;
     g_route_bits |= kRouteExact;
     hipLaunchKernelGGL(kt, grid, dim3(256), lds, s, a);
     return hipGetLastError();

@@ -29,6 +29,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "sd_device.h"
 #include "sd_gl4_args.h"
 #include "sd_gl4_lds.h"
 #include "sd_internal.h"
@@ -37,26 +38,10 @@
 
 namespace sd {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx8 __attribute__((ext_vector_type(8)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(3))) float lds_float;
 typedef __attribute__((address_space(3))) floatx4 lds_floatx4;
-
-template <int N>
-struct VmCnt4 {
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    static constexpr int imm = (N & 0xF) | (0x7 << 4) | (0xF << 8) | ((N >> 4) << 14);
-};
-
-__device__ __forceinline__ floatx4 g4(const float* p) { return *reinterpret_cast<const floatx4*>(p); }
 
 // a compile-time index as a lambda argument (a store's piece: its offset is the instruction's immediate)
 template <int V>
@@ -339,8 +324,8 @@ __global__ __launch_bounds__(256) void k_gl4y(const GL4GArgs p) {
             src = p.x2_blk ? x2r + ((k0 - p.K1) << 5) : x2r + (k0 - p.K1);
             step4 = p.x2_blk ? 128 : 4;
         }
-        xa[sl] = g4(src);
-        xb[sl] = g4(src + step4);
+        xa[sl] = ld4(src);
+        xb[sl] = ld4(src + step4);
         const _Float16* w = wbase + c * wcs;
         wh[sl] = *reinterpret_cast<const halfx8*>(w);
         if constexpr (!PREC) wl[sl] = *reinterpret_cast<const halfx8*>(w + 512);
@@ -610,8 +595,8 @@ __device__ __forceinline__ void gl4t_body(const GL4GArgs& p, const Unit3 un, con
                 const bool bsrc = c < c1 ? p.x1_bf16 : p.x2_bf16;
                 const float* base = c < c1 ? p.x1 : p.x2;
                 const float* qb = reinterpret_cast<const float*>(reinterpret_cast<const __bf16*>(base) + (src - base));
-                xa[s][rt] = g4(bsrc ? qb : src);
-                xb[s][rt] = g4(bsrc ? qb : src + xstep(c));
+                xa[s][rt] = ld4(bsrc ? qb : src);
+                xb[s][rt] = ld4(bsrc ? qb : src + xstep(c));
             }
         }
     };
@@ -686,18 +671,18 @@ __device__ __forceinline__ void gl4t_body(const GL4GArgs& p, const Unit3 un, con
     // the whole-unrolled loop, so the switch folds)
     auto wait_chunk = [&](int c, int younger) {
         switch (younger) {
-            case 0: __builtin_amdgcn_s_waitcnt(VmCnt4<0>::imm & ~(0xF << 8)); break;
+            case 0: __builtin_amdgcn_s_waitcnt(VmCnt<0>::imm & ~(0xF << 8)); break;
             case 1:
-                if (wa) __builtin_amdgcn_s_waitcnt(VmCnt4<OPA>::imm & ~(0xF << 8));
-                else __builtin_amdgcn_s_waitcnt(VmCnt4<OPB>::imm & ~(0xF << 8));
+                if (wa) __builtin_amdgcn_s_waitcnt(VmCnt<OPA>::imm & ~(0xF << 8));
+                else __builtin_amdgcn_s_waitcnt(VmCnt<OPB>::imm & ~(0xF << 8));
                 break;
             case 2:
-                if (wa) __builtin_amdgcn_s_waitcnt(VmCnt4<2 * OPA>::imm & ~(0xF << 8));
-                else __builtin_amdgcn_s_waitcnt(VmCnt4<2 * OPB>::imm & ~(0xF << 8));
+                if (wa) __builtin_amdgcn_s_waitcnt(VmCnt<2 * OPA>::imm & ~(0xF << 8));
+                else __builtin_amdgcn_s_waitcnt(VmCnt<2 * OPB>::imm & ~(0xF << 8));
                 break;
             default:
-                if (wa) __builtin_amdgcn_s_waitcnt(VmCnt4<3 * OPA>::imm & ~(0xF << 8));
-                else __builtin_amdgcn_s_waitcnt(VmCnt4<3 * OPB>::imm & ~(0xF << 8));
+                if (wa) __builtin_amdgcn_s_waitcnt(VmCnt<3 * OPA>::imm & ~(0xF << 8));
+                else __builtin_amdgcn_s_waitcnt(VmCnt<3 * OPB>::imm & ~(0xF << 8));
                 break;
         }
         if constexpr (XV) {
@@ -1095,9 +1080,8 @@ __device__ __forceinline__ void gl4_body(const A& p, const int bx, const int nwg
         ctile = (int)r;
         row0 = (int64_t)q * 32;
     } else {
-        const int xcd = bx & 7, q8 = nwg >> 3, r8 = nwg & 7;
         const int ntile_c = ATT ? p.attn_heads : (p.N + COLS - 1) / COLS;
-        L = (MODE == 1 && p.attn_order == 1) ? (int)bx : (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bx >> 3);
+        L = (MODE == 1 && p.attn_order == 1) ? (int)bx : (int)xcd_remap(bx, nwg >> 3, nwg & 7);
         ctile = L % ntile_c;
         row0 = (int64_t)(L / ntile_c) * (32 * RT);
         nchunk = (p.K1 + p.K2) >> 4;  // even (checked at launch)
@@ -1171,7 +1155,7 @@ __device__ __forceinline__ void gl4_body(const A& p, const int bx, const int nwg
                                                      *reinterpret_cast<const bf16x4*>(reinterpret_cast<const __bf16*>(p.res) + ro), floatx4)
                                                : floatx4{0.f, 0.f, 0.f, 0.f};
                 else
-                    rv[kk][ib] = (ok && i < J) ? g4(p.res + ro) : floatx4{0.f, 0.f, 0.f, 0.f};
+                    rv[kk][ib] = (ok && i < J) ? ld4(p.res + ro) : floatx4{0.f, 0.f, 0.f, 0.f};
             }
         }
     };
@@ -1211,7 +1195,7 @@ __device__ __forceinline__ void gl4_body(const A& p, const int bx, const int nwg
             const int q = tid + k * NTH;
             float* d;
             if (q < YQ) {
-                yv[k] = g4(ysrc(q, d));
+                yv[k] = ld4(ysrc(q, d));
             }
         }
         if constexpr (MODE == 2 && RES_EARLY)  // the residual in flight with the slab (one memory latency)
@@ -1281,8 +1265,8 @@ __device__ __forceinline__ void gl4_body(const A& p, const int bx, const int nwg
                     const __bf16* bs = reinterpret_cast<const __bf16*>(base) + (src - base);
                     xb.a[m][rt] = *reinterpret_cast<const floatx4*>(bs);
                 } else {
-                    xb.a[m][rt] = g4(src);
-                    xb.b[m][rt] = g4(src + step4);
+                    xb.a[m][rt] = ld4(src);
+                    xb.b[m][rt] = ld4(src + step4);
                 }
             }
     };
@@ -1374,7 +1358,7 @@ __device__ __forceinline__ void gl4_body(const A& p, const int bx, const int nwg
     // is a builtin (not inline asm) so the compiler knows x(c) is complete and inserts no
     // further vmcnt waits before the MFMAs.
     auto step = [&](int c, const XBuf& cur, XBuf& nxt) {
-        __builtin_amdgcn_s_waitcnt(VmCnt4<0>::imm);
+        __builtin_amdgcn_s_waitcnt(VmCnt<0>::imm);
         __builtin_amdgcn_s_barrier();
         if (c + 1 < nchunk) {
             fill_w(c + 1, (c & 1) ? sW0 : sW1);
@@ -1666,14 +1650,11 @@ static hipError_t gl4_launch_t(const GLArgs& a, bool rms, hipStream_t s) {
     const int64_t ntile_r = (a.B + 32 * RT - 1) / (32 * RT);
     const dim3 grid((unsigned)(ntile_c * ntile_r * (MODE == 2 ? 2 : MODE == 3 ? 4 : 1)));
     const size_t lds = gl4_lds(J, CT, MODE, PREC, a.ntypes).bytes;
-    if (lds > kGl4LdsMax) return hipErrorNotSupported;
+    if (lds > kLdsMax) return hipErrorNotSupported;
     // Every launch takes exactly the LDS it uses and may share its CU with other kernels' workgroups (row
     // chains, concurrent plans): the hazard there was the update kernel's packed FP32
     auto launch = [&](auto k, const auto& args, unsigned route) {
-        if (lds > kGl4LdsDefault) {
-            hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
+        if (const hipError_t e = lds_opt_in(k, lds); e != hipSuccess) return e;
         g_route_bits |= route;
         hipLaunchKernelGGL(k, grid, dim3(NW * 64), lds, s, args);
         return hipGetLastError();
@@ -1896,7 +1877,7 @@ static hipError_t gl4_pair(const GLArgs& pr, const GLArgs& a, const GLArgs& b, h
     GL4PairArgs pp;
     if (!pack_gl4_pair(a, b, &pp)) return hipErrorInvalidValue;
     constexpr size_t lds = gl4_lds(J, 1, 2, 0, 0).bytes;  // k_gl4m's MODE 2 tile (any PREC)
-    static_assert(lds <= kGl4LdsDefault, "default dynamic LDS");
+    static_assert(lds <= kLdsDefault, "default dynamic LDS");
     g_route_bits |= kRouteMixPhase;
     if (pr.prec == 2) hipLaunchKernelGGL((k_gl4_pair<J, 2>), grid, dim3(512), lds, s, pp);
     else hipLaunchKernelGGL((k_gl4_pair<J, 0>), grid, dim3(512), lds, s, pp);

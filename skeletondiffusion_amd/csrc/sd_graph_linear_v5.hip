@@ -20,20 +20,11 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "sd_device.h"
 #include "sd_internal.h"
 
 namespace sd {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef unsigned uint4v __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
-template <int N>
-struct VmC {  // s_waitcnt vmcnt(N), expcnt / lgkmcnt not waited
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    static constexpr int imm = (N & 0xF) | (0x7 << 4) | (0xF << 8) | ((N >> 4) << 14);
-};
 
 constexpr int TM = 64, TN = 64, TK = 32;
 
@@ -89,7 +80,7 @@ __global__ __launch_bounds__(256) void k_gl5_gemm(const GLArgs p, float* __restr
     const int K = p.K1 + p.K2;
     const float* W = p.W + (int64_t)p.wrow[j] * K;
 
-    f32x16 acc;
+    floatx16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     float ssq[2] = {0.f, 0.f};
@@ -296,7 +287,7 @@ __global__ __launch_bounds__(256) void k_gl5_mixm(const GLArgs p, const float* z
             for (int s = 0; s < 16; ++s) {
                 if (s < KS) {  // wave-uniform
                     const float a = s_z[sl * SLAB + (4 * s + l4) * ZS + 16 * cb + l16];
-                    t = __builtin_amdgcn_mfma_f32_16x16x4f32(a, gb[s], t, 0, 0, 0);
+                    t = mfma4(a, gb[s], t);
                 }
             }
             acc[cb] = t;
@@ -425,13 +416,13 @@ __global__ __launch_bounds__(256, 2) void k_gl5_mixd(const GLArgs p, const float
         const int n = younger_fills * FO + younger_stores * ST;
         // a switch over the possible immediates (n <= (PF - 1) * 8 + PF * 4)
         switch (n) {
-#define SD_VMC(v) case v: __builtin_amdgcn_s_waitcnt(VmC<v>::imm); break;
+#define SD_VMC(v) case v: __builtin_amdgcn_s_waitcnt(VmCnt<v>::imm); break;
             SD_VMC(0) SD_VMC(1) SD_VMC(2) SD_VMC(3) SD_VMC(4) SD_VMC(5) SD_VMC(6) SD_VMC(7) SD_VMC(8) SD_VMC(9)
             SD_VMC(10) SD_VMC(11) SD_VMC(12) SD_VMC(13) SD_VMC(14) SD_VMC(15) SD_VMC(16) SD_VMC(17) SD_VMC(18)
             SD_VMC(19) SD_VMC(20) SD_VMC(21) SD_VMC(22) SD_VMC(23) SD_VMC(24) SD_VMC(25) SD_VMC(26) SD_VMC(27)
             SD_VMC(28) SD_VMC(29) SD_VMC(30) SD_VMC(31) SD_VMC(32)
 #undef SD_VMC
-            default: __builtin_amdgcn_s_waitcnt(VmC<0>::imm); break;
+            default: __builtin_amdgcn_s_waitcnt(VmCnt<0>::imm); break;
         }
         asm volatile("" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -477,7 +468,7 @@ __global__ __launch_bounds__(256, 2) void k_gl5_mixd(const GLArgs p, const float
 #pragma unroll
                 for (int cb = 0; cb < 4; ++cb) {
                     const float a = zs[row * 64 + ((((16 * cb + l16) >> 2) ^ ((l4 & 1) << 2)) << 2) + (l16 & 3)];
-                    acc[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, gb[s], acc[cb], 0, 0, 0);
+                    acc[cb] = mfma4(a, gb[s], acc[cb]);
                 }
             }
         }
@@ -498,11 +489,11 @@ __global__ __launch_bounds__(256, 2) void k_gl5_mixd(const GLArgs p, const float
                 v[e] = v[e] + rvv[e];
             }
             const int off = live ? (int)((r * p.out_rs + (int64_t)i * N + n0 + 16 * cb + 4 * l4) * 4) : 0x7ffffff0;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, make_float4(v[0], v[1], v[2], v[3])), orsrc,
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uintx4, make_float4(v[0], v[1], v[2], v[3])), orsrc,
                                                    off, 0, 0);
         }
     }
-    __builtin_amdgcn_s_waitcnt(VmC<0>::imm);  // the trailing (clamped) fills land before LDS is released
+    __builtin_amdgcn_s_waitcnt(VmCnt<0>::imm);  // the trailing (clamped) fills land before LDS is released
 }
 
 }  // namespace
@@ -578,10 +569,7 @@ hipError_t launch_graph_linear_v5(const GLArgs& a, bool rms, hipStream_t s) {
         const int KS = (a.J + 3) / 4;
         auto launch = [&](auto kt, int R, int PF) -> hipError_t {
             const size_t lds = (size_t)(PF + 1) * (a.res ? 2 : 1) * 4 * KS * 64 * sizeof(float);
-            if (lds > 64 * 1024) {
-                const hipError_t e = hipFuncSetAttribute((const void*)kt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) return e;
-            }
+            if (const hipError_t e = lds_opt_in(kt, lds); e != hipSuccess) return e;
             hipLaunchKernelGGL(kt, dim3((unsigned)((a.B + R - 1) / R), (unsigned)(a.N / 64)), dim3(256), lds, s, a,
                                (const float*)z, z_rs);
             return hipGetLastError();

@@ -1,5 +1,5 @@
 // Internal interfaces between the host plan (sd_plan.hip) and the gfx950 kernels
-// (sd_kernels.hip).  Not part of the public ABI (see include/skeldiff.h).
+// (sd_kernels.hip, sd_graph_linear*.hip).  Not part of the public ABI (see include/skeldiff.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,8 +21,9 @@ struct GLArgs {
     int64_t x1_row0;                                      // 0 <= x1_row0 < x1_div (a row chunk's phase)
     int tile_hint;                                        // v4 tile <NW><RT><CT> when gl4_cfg is 0 (0: per shape)
     // per-launch kernel selection (the plan's options, sd_plan_set_option; the sd_test_set_* hooks
-    // for the test entry points): generation 0 auto / 1..5 forced, v4 tile <NW><RT><CT> (0 auto),
-    // v4 weight staging 0 LDS-DMA (CU held exclusively) / 1 register-staged (CU shareable)
+    // for the test entry points): generation 0 auto / 2..5 forced (1: an alias of 2), v4 tile
+    // <NW><RT><CT> (0 auto), v4 weight staging 0 LDS-DMA (CU held exclusively) / 1 register-staged
+    // (CU shareable)
     int variant, gl4_cfg, gl4_stage;
     // v4 split route (phase 1 GEMM per (tile, node) into the zs scratch, phase 2 mixing epilogue;
     // bitwise identical to the one-kernel route): 0 auto, 1 never, 2 k_gl4y, 3 k_gl4t, 4 k_gl4t
@@ -93,7 +94,7 @@ enum RouteBits : unsigned {
     kRouteGemmTiled = 8,   // k_gl4t: tiled split route (and v5) GEMM phase
     kRouteMixPhase = 16,   // k_gl4 MODE 2 / 3: split-route mixing / attention phase
     kRouteV5Mix = 32,      // k_gl5_gemm / k_gl5_mix (J > 21)
-    kRouteExact = 64,      // exact-f32 generations v1-v3
+    kRouteExact = 64,      // exact-f32 generations v2 (also what variant 1 runs) and v3
     kRouteAttention = 128,  // k_attention: the separate attention kernel (J > 21, unfused routes)
     // 256 / 512: round 5's small-batch fused tile and fused layer kernel (removed in round 6)
     kRouteAttnMix = 1024     // k_attention_mix: the to_qkv layer's mixing inside the attention kernel
@@ -137,9 +138,8 @@ struct UpdArgs {
     int elementwise;  // SD_OPT_UPDATE_KERNEL: 0 k_update_mfma where it applies, 1 the element-per-thread forms
 };
 
-hipError_t launch_graph_linear(const GLArgs& a, bool rms, hipStream_t s);     // dispatches v1..v5
+hipError_t launch_graph_linear(const GLArgs& a, bool rms, hipStream_t s);     // dispatches v2..v5 (sd_graph_linear.hip)
 hipError_t launch_graph_linear_v5(const GLArgs& a, bool rms, hipStream_t s);  // J > 21: GEMM + mixing pass
-hipError_t launch_graph_linear_v1(const GLArgs& a, bool rms, hipStream_t s);
 hipError_t launch_graph_linear_v2(const GLArgs& a, bool rms, hipStream_t s);
 hipError_t launch_graph_linear_v3(const GLArgs& a, bool rms, hipStream_t s);  // J in {16,17,21}
 hipError_t launch_graph_linear_v4(const GLArgs& a, bool rms, hipStream_t s);  // needs a.wsp

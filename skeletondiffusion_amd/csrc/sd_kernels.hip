@@ -1,33 +1,28 @@
-// gfx950 (CDNA4, MI355X) kernels for the SkeletonDiffusion reverse-diffusion step.
+// gfx950 (CDNA4, MI355X) kernels of the reverse-diffusion step other than StaticGraphLinear (whose
+// generations and dispatcher are in sd_graph_linear*.hip).
 //
-//   k_graph_linear  StaticGraphLinear + fused epilogue        graph_structural.py:30-43,
-//                   (per-node-type GEMM on v_mfma_f32_16x16x4_f32, bias, G-hat node mixing,
-//                    RMSNorm scale, FiLM, tanh, residual)      attention.py:30-102
-//   k_attention     multi-head attention over joints, QK^T and PV on MFMA   attention.py:122-136
-//   k_update        x0 clamp + C1 x0 + C2 x_t + U (sigma . eps)   nonisotropic.py:196-210,
-//                   base.py:314-341, isotropic.py:85-95
-//   k_noise_fill    counter-based Philox4x32-10 + Box-Muller normals (replaces randn)
-//   plan helpers    sinusoidal embedding, small linears (time MLP / FiLM tables), G-hat,
-//                   RMSNorm gain folding, sigma table
+//   k_attention       multi-head attention over joints, QK^T and PV on MFMA   attention.py:122-136
+//   k_attention_mix   the same with the to_qkv layer's node mixing in front (MANO)
+//   k_update*         x0 clamp + C1 x0 + C2 x_t + U (sigma . eps)   nonisotropic.py:196-210,
+//                     base.py:314-341, isotropic.py:85-95
+//   k_noise_fill      counter-based Philox4x32-10 + Box-Muller normals (replaces randn), the raw
+//                     Philox words and the device seed record
+//   row copies        k_copy_rows, k_convert_rows (f32 <-> bf16)
+//   plan helpers      sinusoidal embedding, small linears (time MLP / FiLM tables), G-hat,
+//                     RMSNorm gain folding, sigma table
 //
 // Layout in HBM: every activation is row-major (rows B, nodes J, features F), F contiguous.
-// All arithmetic is fp32; the GEMMs use the exact-f32 MFMA (a k-ordered fmaf chain).
+// All arithmetic is fp32; the products on the matrix cores use the exact-f32 MFMA (a k-ordered
+// fmaf chain).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sd_device.h"
 #include "sd_internal.h"
 #include "sd_philox.h"
 
 namespace sd {
 
-thread_local unsigned g_route_bits = 0;
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ floatx4 ld4(const float* p) { return *reinterpret_cast<const floatx4*>(p); }
 __device__ __forceinline__ floatx2 ld2(const float* p) { return *reinterpret_cast<const floatx2*>(p); }
 __device__ __forceinline__ void st2(float* p, floatx2 v) { *reinterpret_cast<floatx2*>(p) = v; }
 // a latent pair at element offset `o` of a buffer holding f32 or (bf16 mode) bf16 elements
@@ -38,220 +33,6 @@ __device__ __forceinline__ floatx2 ld2x(const float* p, int64_t o, int bf) {
 __device__ __forceinline__ void st2x(float* p, int64_t o, int bf, floatx2 v) {
     if (bf) *reinterpret_cast<bf16x2*>(reinterpret_cast<__bf16*>(p) + o) = __builtin_convertvector(v, bf16x2);
     else *reinterpret_cast<floatx2*>(p + o) = v;
-}
-
-__device__ __forceinline__ floatx4 mfma4(float a, float b, floatx4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-// =============================================================================================
-// StaticGraphLinear
-//
-// Workgroup = 4 waves; a wave owns 16 rows x (16*NCB) output columns for ALL J nodes, so the
-// G-hat node mixing (which couples the J nodes of a row) happens in registers.
-// MFMA 16x16x4 f32 operand maps (cdna_hip_programming.md §3): lane l supplies
-// A[l&15][k=l>>4] and B[k=l>>4][l&15]; D[row=4*(l>>4)+r][col=l&15].  We permute k inside a
-// 16-wide chunk so each lane reads ONE float4 of x and ONE float4 of W per 4 MFMAs: in step s
-// of chunk kc, position p = l>>4 carries k = kc + 4p + s for both operands.
-// =============================================================================================
-
-template <int JM, bool EXACT, int NCB, bool RMS>
-__device__ __forceinline__ void gl_accumulate(floatx4 (&acc)[JM][NCB], float (&ss)[JM],
-                                              const float* __restrict__ xrow, bool row_ok,
-                                              int Kp, int koff, int K, int J,
-                                              const GLArgs& p, int c0, int lr, int lg) {
-    for (int kc = 0; kc < Kp; kc += 16) {
-#pragma unroll
-        for (int j = 0; j < JM; ++j) {
-            if (!EXACT && j >= J) continue;
-            floatx4 a = row_ok ? ld4(xrow + (int64_t)j * Kp + kc + 4 * lg) : floatx4{0.f, 0.f, 0.f, 0.f};
-            if (RMS) ss[j] += a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w;
-            const float* wb = p.W + (int64_t)p.wrow[j] * K + koff + kc + 4 * lg;
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb) {
-                const int n = c0 + 16 * cb + lr;
-                floatx4 b = (n < p.N) ? ld4(wb + (int64_t)n * K) : floatx4{0.f, 0.f, 0.f, 0.f};
-                floatx4 c = acc[j][cb];
-                c = mfma4(a.x, b.x, c);
-                c = mfma4(a.y, b.y, c);
-                c = mfma4(a.z, b.z, c);
-                c = mfma4(a.w, b.w, c);
-                acc[j][cb] = c;
-            }
-        }
-    }
-}
-
-template <int JM, bool EXACT, int NCB, bool RMS>
-__global__ __launch_bounds__(256) void k_graph_linear(const GLArgs p) {
-    __shared__ float sG[JM * JM];
-    const int J = EXACT ? JM : p.J;
-    for (int i = threadIdx.x; i < J * J; i += 256) sG[i] = p.G[i];
-    __syncthreads();
-
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int lr = lane & 15;
-    const int lg = lane >> 4;
-    const int ntile_c = (p.N + 16 * NCB - 1) / (16 * NCB);
-    const int ct = blockIdx.x % ntile_c;
-    const int64_t rt = blockIdx.x / ntile_c;
-    const int64_t row0 = rt * 64 + wave * 16;
-    if (row0 >= p.B) return;  // whole wave idle (no barrier follows)
-    const int c0 = ct * 16 * NCB;
-    const int K = p.K1 + p.K2;
-
-    floatx4 acc[JM][NCB];
-    float ss[JM];
-#pragma unroll
-    for (int j = 0; j < JM; ++j) {
-        ss[j] = 0.f;
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) acc[j][cb] = floatx4{0.f, 0.f, 0.f, 0.f};
-    }
-
-    const int64_t arow = row0 + lr;
-    const bool row_ok = arow < p.B;
-    const int64_t arow_c = row_ok ? arow : 0;
-    gl_accumulate<JM, EXACT, NCB, RMS>(acc, ss, p.x1 + ((arow_c + p.x1_row0) / p.x1_div) * p.x1_rs, row_ok,
-                                       p.K1, 0, K, J, p, c0, lr, lg);
-    if (p.K2 > 0) {
-        float dummy[JM];
-        gl_accumulate<JM, EXACT, NCB, false>(acc, dummy, p.x2 + arow_c * p.x2_rs, row_ok,
-                                             p.K2, p.K1, K, J, p, c0, lr, lg);
-    }
-
-    if (RMS) {  // F.normalize(x, dim=-1): scale row (b, j) by 1 / max(||x_bj||, 1e-12)
-#pragma unroll
-        for (int j = 0; j < JM; ++j) {
-            if (!EXACT && j >= J) continue;
-            float t = ss[j];
-            t += __shfl_xor(t, 16);
-            t += __shfl_xor(t, 32);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float n2 = __shfl(t, 4 * lg + r);
-                const float s = 1.0f / fmaxf(sqrtf(n2), 1e-12f);
-#pragma unroll
-                for (int cb = 0; cb < NCB; ++cb) acc[j][cb][r] *= s;
-            }
-        }
-    }
-    if (p.bias) {  // bias added per source node BEFORE the mixing (graph_structural.py:38-41)
-#pragma unroll
-        for (int j = 0; j < JM; ++j) {
-            if (!EXACT && j >= J) continue;
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb) {
-                const int n = c0 + 16 * cb + lr;
-                const float bv = (n < p.N) ? p.bias[p.wrow[j] + n] : 0.f;
-                acc[j][cb] += bv;
-            }
-        }
-    }
-
-    float fa[NCB], fb[NCB];
-#pragma unroll
-    for (int cb = 0; cb < NCB; ++cb) {
-        const int n = c0 + 16 * cb + lr;
-        fa[cb] = 1.f;
-        fb[cb] = 0.f;
-        if (p.film && n < p.N) {
-            fa[cb] = p.film[n] + 1.0f;
-            fb[cb] = p.film[p.N + n];
-        }
-    }
-
-    for (int i = 0; i < J; ++i) {
-        floatx4 z[NCB];
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) z[cb] = floatx4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < JM; ++j) {
-            if (!EXACT && j >= J) continue;
-            const float g = sG[i * J + j];
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb) z[cb] += g * acc[j][cb];
-        }
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) {
-            const int n = c0 + 16 * cb + lr;
-            if (n >= p.N) continue;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int64_t row = row0 + 4 * lg + r;
-                if (row >= p.B) continue;
-                float v = z[cb][r];
-                if (p.film) v = v * fa[cb] + fb[cb];
-                if (p.act == 1) v = tanhf(v);
-                if (p.res) v += p.res[row * p.res_rs + (int64_t)i * p.N + n];
-                p.out[row * p.out_rs + (int64_t)i * p.N + n] = v;
-            }
-        }
-    }
-}
-
-template <int JM, bool EXACT, int NCB>
-static hipError_t gl_dispatch_rms(const GLArgs& a, bool rms, hipStream_t s) {
-    const int ntile_c = (a.N + 16 * NCB - 1) / (16 * NCB);
-    const int64_t ntile_r = (a.B + 63) / 64;
-    const dim3 grid((unsigned)(ntile_c * ntile_r));
-    g_route_bits |= kRouteExact;
-    if (rms)
-        hipLaunchKernelGGL((k_graph_linear<JM, EXACT, NCB, true>), grid, dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL((k_graph_linear<JM, EXACT, NCB, false>), grid, dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-// 0 (default): v4 (f32-accurate split-f16 MFMA) where the plan prepared split weights and the
-// skeleton has an instantiation; otherwise the exact-f32 kernels per shape: v3 (node-split
-// waves, 32x32 f32 MFMA) for N < 512, where it measured 1.15-1.25x faster than v2; v2 with
-// 32-column tiles for the wide to_qkv layer (N = 768); v5 (node-batched GEMM + mixing pass) for
-// J > 21, where every one-kernel tile must stage all node types' weights.  1..5 force one
-// generation (falling through to v2 where the forced one does not apply).
-hipError_t launch_graph_linear(const GLArgs& a, bool rms, hipStream_t s) {
-    const int v = a.variant;
-    // every generation computes a column tile from the whole K extent of its rows: an input that
-    // aliases the output would be overwritten by sibling column tiles while still being read
-    if (a.B > 0 && (a.x1 == a.out || (a.x2 && a.x2 == a.out))) return hipErrorInvalidValue;
-    if (a.skip_mix) return (v == 0 || v == 5) && a.J > 21 && a.prec != 2 ? launch_graph_linear_v5(a, rms, s) : hipErrorNotSupported;
-    // Block.norm 'layer' lives in the v4 mixing epilogue only (J = 16 / 17 / 21; plan-time checked)
-    if (a.ln_w) return v == 0 || v == 4 ? launch_graph_linear_v4(a, rms, s) : hipErrorNotSupported;
-    if (v == 1) return launch_graph_linear_v1(a, rms, s);
-    if (v == 4 || v == 0) {
-        const hipError_t e = launch_graph_linear_v4(a, rms, s);
-        if (e != hipErrorNotSupported) return e;
-    }
-    // bf16 operands (precision mode 2) exist only in the v4 tiles: no exact-f32 fallback
-    if (a.prec == 2 || a.x1_bf16 || a.x2_bf16 || a.res_bf16 || a.out_bf16) return hipErrorNotSupported;
-    // the exact-f32 generations read and write row-major activations only
-    if (a.x1_blk || a.x2_blk || a.res_blk || a.out_blk) return hipErrorNotSupported;
-    // large skeletons (J > 21, MANO J = 51: 43 node types): node-batched GEMM + mixing pass
-    if (v == 5 || (v == 0 && a.J > 21)) {
-        const hipError_t e = launch_graph_linear_v5(a, rms, s);
-        if (e != hipErrorNotSupported) return e;
-    }
-    if (v == 3 || (v == 0 && a.N < 512)) {
-        const hipError_t e = launch_graph_linear_v3(a, rms, s);
-        if (e != hipErrorNotSupported) return e;
-    }
-    return launch_graph_linear_v2(a, rms, s);
-}
-
-hipError_t launch_graph_linear_v1(const GLArgs& a, bool rms, hipStream_t s) {
-    if (a.B <= 0) return hipSuccess;
-    switch (a.J) {
-        case 16: return gl_dispatch_rms<16, true, 2>(a, rms, s);
-        case 17: return gl_dispatch_rms<17, true, 2>(a, rms, s);
-        case 21: return gl_dispatch_rms<21, true, 2>(a, rms, s);
-        case 51: return gl_dispatch_rms<51, true, 1>(a, rms, s);
-        default: break;
-    }
-    if (a.J <= 8) return gl_dispatch_rms<8, false, 2>(a, rms, s);
-    if (a.J <= 16) return gl_dispatch_rms<16, false, 2>(a, rms, s);
-    if (a.J <= 32) return gl_dispatch_rms<32, false, 1>(a, rms, s);
-    return gl_dispatch_rms<64, false, 1>(a, rms, s);
 }
 
 // =============================================================================================
@@ -1067,12 +848,9 @@ hipError_t launch_update(const UpdArgs& a, hipStream_t s) {
     if (g_update_mfma && !a.iso && a.J > 32 && a.J <= 64 && a.D % 16 == 0 && (a.D / 16 + 3) / 4 <= 2) {
         // J <= 64 (MANO J = 51 / 52): one row per workgroup, each wave at most two column tiles
         const size_t lds = (((3 * 64 * 66 + 3) & ~(size_t)3) + (size_t)a.J * (a.D + 16)) * sizeof(float);
-        if (lds > 160 * 1024) return hipErrorNotSupported;
+        if (lds > kLdsMax) return hipErrorNotSupported;
         auto kern = (a.x0_bf16 || a.xt_bf16) ? k_update_mfma<64, 1, 2, true> : k_update_mfma<64, 1, 2>;
-        if (lds > 64 * 1024) {
-            const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
+        if (const hipError_t e = lds_opt_in(kern, lds); e != hipSuccess) return e;
         hipLaunchKernelGGL(kern, dim3((unsigned)a.B), dim3(256), lds, s, a);
         return hipGetLastError();
     }
@@ -1084,11 +862,8 @@ hipError_t launch_update(const UpdArgs& a, hipStream_t s) {
         const dim3 grid((unsigned)((a.B + R - 1) / R));
         auto go = [&](auto kern, int JP) -> hipError_t {
             const size_t lds = (((3 * (size_t)JP * (JP + 2) + 3) & ~(size_t)3) + (size_t)R * a.J * (a.D + 16)) * sizeof(float);
-            if (lds > 160 * 1024) return hipErrorNotSupported;
-            if (lds > 64 * 1024) {
-                const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) return e;
-            }
+            if (lds > kLdsMax) return hipErrorNotSupported;
+            if (const hipError_t e = lds_opt_in(kern, lds); e != hipSuccess) return e;
             hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
             return hipGetLastError();
         };
@@ -1102,7 +877,7 @@ hipError_t launch_update(const UpdArgs& a, hipStream_t s) {
     if (a.B <= kUpdateRows && a.D % 2 == 0) {
         const size_t nt = a.iso ? 0 : 3 * (size_t)a.J * a.J + a.J;
         const size_t lds = (((nt + 3) & ~(size_t)3) + 3 * (size_t)a.J * a.D) * sizeof(float);
-        if (lds <= 64 * 1024) {
+        if (lds <= kLdsDefault) {
             hipLaunchKernelGGL(k_update_row, dim3((unsigned)a.B), dim3(256), lds, s, a);
             return hipGetLastError();
         }

@@ -40,8 +40,6 @@ namespace {
 
 using namespace motion;
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
 struct MotionArgs {
     const float* frames; int64_t total_frames;
     const int64_t* seg_first; int64_t nseg;

@@ -9,9 +9,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace sd {
+#include "sd_device.h"
 
-typedef float floatx2 __attribute__((ext_vector_type(2)));
+namespace sd {
 
 __device__ __forceinline__ uint4 philox(uint4 c, uint32_t k0, uint32_t k1) {
 #pragma unroll

@@ -28,8 +28,6 @@ namespace {
 
 using namespace qsample;
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
 struct QSampleArgs {
     const float* x0; const int64_t* t; const float* sqrt_ac; const float* M; const float* sqrt_1mac;
     int T, k, J, D;

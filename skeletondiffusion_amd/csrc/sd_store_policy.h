@@ -23,10 +23,9 @@
 //   * LDS: the compiler moves no LDS read across volatile asm.  What feeds the NEXT store from LDS is read,
 //     in the source, before this one.
 #pragma once
+#include "sd_device.h"
 
 namespace sd {
-
-typedef float store_floatx4 __attribute__((ext_vector_type(4)));
 
 constexpr int kStorePlain = 0;         // write-back: the line stays, dirty, in the XCD's L2
 constexpr int kStoreWriteThrough = 1;  // sc1: written through, the line dropped
@@ -37,13 +36,13 @@ constexpr int kStoreGemmY = kStoreWriteThrough;  // GEMM-phase Y into the row-bl
 // p + BYTE_OFF: an immediate of the instruction (-4096 .. 4095), so constant pieces of a tile cost no
 // address arithmetic
 template <int POLICY, int BYTE_OFF = 0>
-__device__ __forceinline__ void store16(float* p, store_floatx4 v) {
+__device__ __forceinline__ void store16(float* p, floatx4 v) {
     static_assert(POLICY == kStorePlain || POLICY == kStoreWriteThrough, "store policy");
     static_assert(BYTE_OFF >= -4096 && BYTE_OFF < 4096 && BYTE_OFF % 16 == 0, "immediate offset");
     if constexpr (POLICY == kStoreWriteThrough)
         asm volatile("global_store_dwordx4 %0, %1, off offset:%2 sc1\n\ts_nop 1" ::"v"(p), "v"(v), "n"(BYTE_OFF));
     else
-        *reinterpret_cast<store_floatx4*>(reinterpret_cast<char*>(p) + BYTE_OFF) = v;
+        *reinterpret_cast<floatx4*>(reinterpret_cast<char*>(p) + BYTE_OFF) = v;
 }
 
 }  // namespace sd

@@ -19,6 +19,7 @@
 #include <string>
 
 #include "../../include/skeldiff.h"
+#include "sd_device.h"
 #include "sd_internal.h"
 
 namespace sd {
@@ -26,8 +27,6 @@ namespace {
 
 constexpr int TM = 64, TN = 64, TK = 32;
 constexpr int TE = TM * TK / 256;  // staged elements per thread and operand
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // Strided batched GEMM: for batch z (grid.z = nbatch * splits):
 //   node mode (by_type = 0): group = {node j = batch}, t = type(j)
@@ -61,7 +60,7 @@ __device__ __forceinline__ float keep_or_zero(bool ok, float v) {
     return ok ? v : 0.f;
 }
 __device__ __forceinline__ float4 keep_or_zero(bool ok, float4 v) {
-    f32x4 t = {v.x, v.y, v.z, v.w};
+    floatx4 t = {v.x, v.y, v.z, v.w};
     asm volatile("" : "+v"(t));
     return ok ? make_float4(t[0], t[1], t[2], t[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
@@ -170,7 +169,7 @@ __global__ __launch_bounds__(256) void k_gemm(GemmArgs g) {
     const int kbeg = split * g.kchunk;
     const int kend = min(g.K, kbeg + g.kchunk);
 
-    f32x16 acc;
+    floatx16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 
@@ -329,7 +328,7 @@ __global__ __launch_bounds__(256) void k_dghat_part(const float* __restrict__ dy
     __shared__ float s_acc[TI * 32][TI * 32 + 1];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int li = lane & 31, h = lane >> 5;
-    f32x16 acc[TI][TI];
+    floatx16 acc[TI][TI];
 #pragma unroll
     for (int a = 0; a < TI; ++a)
 #pragma unroll
@@ -403,7 +402,7 @@ __global__ __launch_bounds__(256) void k_dghat_part16(const float* __restrict__ 
     __shared__ float s_acc[16][17];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int i = lane & 15, kq = lane >> 4;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    floatx4 acc = {0.f, 0.f, 0.f, 0.f};
     const int64_t r0 = (int64_t)blockIdx.x * rows_per_chunk;
     const int64_t r1 = min(rows, r0 + rows_per_chunk);
     for (int64_t r = r0 + w; r < r1; r += 4) {
@@ -935,11 +934,8 @@ int sd_attn_train_forward(const float* qkv, float* out, int64_t rows, int32_t J,
     if (!qkv || !out) return sd::set_error(SD_E_INVALID, "sd_attn_train_forward: null buffer");
     if (rows * heads > 0x7fffffffLL) return sd::set_error(SD_E_INVALID, "sd_attn_train_forward: too many rows");
     const size_t lds = sd::attn_train_lds(J, dim_head, false);
-    if (lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute((const void*)sd::k_attn_train<false>,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return sd::set_error(SD_E_HIP, std::string("k_attn_train: ") + hipGetErrorString(e));
-    }
+    if (const hipError_t e = sd::lds_opt_in(sd::k_attn_train<false>, lds); e != hipSuccess)
+        return sd::set_error(SD_E_HIP, std::string("k_attn_train: ") + hipGetErrorString(e));
     hipLaunchKernelGGL(sd::k_attn_train<false>, dim3((unsigned)(rows * heads)), dim3(256), lds, (hipStream_t)stream,
                        qkv, (const float*)nullptr, out, J, heads, dim_head, scale);
     const hipError_t e = hipGetLastError();
@@ -954,11 +950,8 @@ int sd_attn_train_backward(const float* qkv, const float* dout, float* dqkv, int
     if (!qkv || !dout || !dqkv) return sd::set_error(SD_E_INVALID, "sd_attn_train_backward: null buffer");
     if (rows * heads > 0x7fffffffLL) return sd::set_error(SD_E_INVALID, "sd_attn_train_backward: too many rows");
     const size_t lds = sd::attn_train_lds(J, dim_head, true);
-    if (lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute((const void*)sd::k_attn_train<true>,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return sd::set_error(SD_E_HIP, std::string("k_attn_train: ") + hipGetErrorString(e));
-    }
+    if (const hipError_t e = sd::lds_opt_in(sd::k_attn_train<true>, lds); e != hipSuccess)
+        return sd::set_error(SD_E_HIP, std::string("k_attn_train: ") + hipGetErrorString(e));
     hipLaunchKernelGGL(sd::k_attn_train<true>, dim3((unsigned)(rows * heads)), dim3(256), lds, (hipStream_t)stream,
                        qkv, dout, dqkv, J, heads, dim_head, scale);
     const hipError_t e = hipGetLastError();
@@ -1057,9 +1050,7 @@ int sd_mahalanobis_loss_forward(const float* model_out, const float* target, con
         return sd::set_error(SD_E_INVALID, "sd_mahalanobis_loss_forward: null buffer");
     if (rows > 0x7fffffffLL) return sd::set_error(SD_E_INVALID, "sd_mahalanobis_loss_forward: too many rows");
     const size_t lds = sd::mahalanobis_lds(J, F);
-    if (lds > 64 * 1024)
-        SD_HIP(hipFuncSetAttribute((const void*)sd::k_mahalanobis<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
+    SD_HIP(sd::lds_opt_in(sd::k_mahalanobis<false>, lds));
     hipLaunchKernelGGL(sd::k_mahalanobis<false>, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream, model_out,
                        target, S, t, T, (const float*)nullptr, loss, J, F, pred_noise ? -1.f : 1.f, mse);
     const hipError_t e = hipGetLastError();
@@ -1076,9 +1067,7 @@ int sd_mahalanobis_loss_backward(const float* model_out, const float* target, co
         return sd::set_error(SD_E_INVALID, "sd_mahalanobis_loss_backward: null buffer");
     if (rows > 0x7fffffffLL) return sd::set_error(SD_E_INVALID, "sd_mahalanobis_loss_backward: too many rows");
     const size_t lds = sd::mahalanobis_lds(J, F);
-    if (lds > 64 * 1024)
-        SD_HIP(hipFuncSetAttribute((const void*)sd::k_mahalanobis<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
+    SD_HIP(sd::lds_opt_in(sd::k_mahalanobis<true>, lds));
     hipLaunchKernelGGL(sd::k_mahalanobis<true>, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream, model_out,
                        target, S, t, T, dloss, dmodel_out, J, F, pred_noise ? -1.f : 1.f, mse);
     const hipError_t e = hipGetLastError();

@@ -132,8 +132,8 @@ class SamplingEngine:
     # f32-accurate for any finite input.
 
     def set_option(self, name: str, value: int) -> None:
-        """Per-plan kernel option (sd_plan_set_option): "kernel_variant" (0 auto, 1..5),
-        "gl4_tile" (<waves><row tiles><col tiles>, 0 auto), "row_chains" (1..8), "gl4_staging"
+        """Per-plan kernel option (sd_plan_set_option): "kernel_variant" (0 auto, 2..5; 1 is an
+        alias of 2), "gl4_tile" (<waves><row tiles><col tiles>, 0 auto), "row_chains" (1..8), "gl4_staging"
         (0 LDS-DMA, 1 register-staged), "split_route" (0 auto, 1 never, 2 k_gl4y, 3 k_gl4t, 4 k_gl4t
         except to_qkv + attention), "update_kernel" (0 matrix cores, 1 element-per-thread),
         "attention" (0 auto, 2 to_qkv mixing in the attention kernel, 3 separate mixing pass),

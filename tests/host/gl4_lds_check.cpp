@@ -17,6 +17,7 @@
 
 #include <vector>
 
+#include "../../skeletondiffusion_amd/csrc/sd_device.h"
 #include "../../skeletondiffusion_amd/csrc/sd_gl4_lds.h"
 #include "../../skeletondiffusion_amd/csrc/sd_ystore_map.h"
 
@@ -174,7 +175,7 @@ int main() {
     // pinned: MODE 2, J = 16, CT = 1 and MODE 3, J = 16
     CHECK(gl4_lds(16, 1, 2, 0, 0).bytes == 39168, "MODE 2, J = 16: %zu bytes", gl4_lds(16, 1, 2, 0, 0).bytes);
     CHECK(gl4_lds(16, 3, 3, 0, 0).bytes == 52992, "MODE 3, J = 16: %zu bytes", gl4_lds(16, 3, 3, 0, 0).bytes);
-    static_assert(gl4_lds(21, 1, 2, 2, 0).bytes <= kGl4LdsDefault, "k_gl4_pair: default dynamic LDS");
+    static_assert(gl4_lds(21, 1, 2, 2, 0).bytes <= kLdsDefault, "k_gl4_pair: default dynamic LDS");
     printf("gl4 lds layout ok (%ld layouts, %ld offsets)\n", n_layouts, n_offsets);
     return 0;
 }

@@ -9,7 +9,7 @@ import glob
 import re
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--kernel", default=r"k_gl|k_graph_linear")
+ap.add_argument("--kernel", default=r"k_gl")
 ap.add_argument("--dir", required=True, help="output directory of a tag's passes; {tag} is replaced")
 ap.add_argument("--raw", action="store_true", help="also print every counter's per-dispatch average")
 ap.add_argument("tags", nargs="+")
