@@ -320,7 +320,8 @@ hipError_t launch_mix(const float* in, const float* ghat, float* out, int64_t ro
 // 32-node tile, half h = l >> 5) loads 4 consecutive features k = k0 + 4h + s of its dy and z rows
 // (16 B) and feeds them as MFMA k-step s: A and B use the same k permutation, so the sum over k
 // is exact.  TI x TI 32x32 tiles cover J <= 32 * TI.  The 4 waves' tiles are summed in LDS in wave
-// order (deterministic).
+// order (deterministic).  The 16-B loads need N % 8 == 0 and 16-B aligned dy and z (a row is then
+// N * 4 bytes, a multiple of 32); any other call takes the masked 4-byte loads.
 template <int TI>
 __global__ __launch_bounds__(256) void k_dghat_part(const float* __restrict__ dy, const float* __restrict__ z,
                                                     float* __restrict__ part, int64_t rows, int J, int N,
@@ -337,7 +338,7 @@ __global__ __launch_bounds__(256) void k_dghat_part(const float* __restrict__ dy
             for (int q = 0; q < 16; ++q) acc[a][b][q] = 0.f;
     const int64_t r0 = (int64_t)blockIdx.x * rows_per_chunk;
     const int64_t r1 = min(rows, r0 + rows_per_chunk);
-    const bool vec = (N & 7) == 0;
+    const bool vec = (N & 7) == 0 && (((uintptr_t)dy | (uintptr_t)z) & 15) == 0;  // uniform
     for (int64_t r = r0 + w; r < r1; r += 4) {
         const float* dyr = dy + r * J * N;
         const float* zr = z + r * J * N;
@@ -395,7 +396,7 @@ __global__ __launch_bounds__(256) void k_dghat_part(const float* __restrict__ dy
 // quarters of its products on padding): lane (node i = l & 15, quad kq = l >> 4) loads features
 // k0 + 16u + 4kq .. +3 of its dy and z rows (16 B each, four 16-feature steps in flight) and feeds
 // them as four k-steps; A and B share the permutation, so the sum over features is exact.
-// One row per wave at a time; the 4 waves' tiles are summed in LDS in wave order.  N % 4 == 0.
+// One row per wave at a time; the 4 waves' tiles are summed in LDS in wave order.  N % 4 == 0, dy and z 16-B aligned.
 __global__ __launch_bounds__(256) void k_dghat_part16(const float* __restrict__ dy, const float* __restrict__ z,
                                                       float* __restrict__ part, int64_t rows, int J, int N,
                                                       int rows_per_chunk) {
@@ -878,7 +879,10 @@ int sd_gl_train_backward(const float* x, const float* z, const float* dy, const 
     // dghat first (reads dy and z, independent of dz)
     if (dghat) {
         const int64_t chunks = sd::ceil_div(rows, sd::kDghatRows);
-        if (J <= 16 && (N & 3) == 0)
+        // k_dghat_part16 has 16-B loads only: N % 4 == 0 and 16-B aligned dy and z, as gemm_vec_ok
+        // and launch_mix_mfma ask of their operands (the ABI states no alignment)
+        const bool aligned16 = (((uintptr_t)dy | (uintptr_t)z) & 15) == 0;
+        if (J <= 16 && (N & 3) == 0 && aligned16)
             hipLaunchKernelGGL(sd::k_dghat_part16, dim3((unsigned)chunks), dim3(256), 0, s, dy, z, part, rows, J, N,
                                sd::kDghatRows);
         else if (J <= 32)

@@ -214,6 +214,27 @@ def test_gl_train_abi_validation_on_host():
                                   None, 0, None) < 0                                                  # null input
 
 
+def test_gl_train_workspace_bytes_sweep():
+    """sd_gl_train_workspace_bytes over the shape table of tests/train_cases.py and the row counts round every
+    chunk edge (4 rows per dghat partial, 16 per dbias partial, 256 per dW split, the 32-split cap): dz plus the
+    largest of the three partial buffers, with splits = clamp(ceil(rows / 256), 1, 32) restated here."""
+    import train_cases
+    from skeletondiffusion_amd import _lib
+    L = _lib.lib()
+    ceil = lambda a, b: -(-a // b)
+    shapes = sorted({(J, K, N, nt) for J, K, N, nt, _ in train_cases.GL_CASES})
+    all_rows = sorted(set(train_cases.SWEEP_ROWS) | {rows for *_, rows in train_cases.GL_CASES})
+    assert {1, 4, 5, 16, 17, 256, 257, 8192, 8193} <= set(all_rows)
+    for J, K, N, nt in shapes:
+        for rows in all_rows:
+            splits = min(max(ceil(rows, 256), 1), 32)
+            types = max(nt, 1)
+            part = max(splits * types * N * K, ceil(rows, 4) * J * J, ceil(rows, 16) * types * N)
+            want = 4 * (rows * J * N + part)
+            assert L.sd_gl_train_workspace_bytes(rows, J, K, N, nt) == want, (rows, J, K, N, nt)
+            assert train_cases.workspace_bytes(rows, J, K, N, nt) == want
+
+
 def _ref_attention(qkv, heads, dh, scale):
     """The reference's attention core (attention.py:122-136) on (rows, J, 3 heads dh)."""
     b, n, _ = qkv.shape
