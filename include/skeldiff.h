@@ -417,6 +417,54 @@ int sd_diverse_rank(const float* pred, const float* target, int64_t nseq, int32_
 int sd_class_sum(const float* values, const int64_t* cls, int64_t rows, int32_t width, int32_t classes, double* sum,
                  int64_t* count, int64_t* total, void* stream);
 
+/* Validation metrics of the training loops (reference src/train_utils.py:56-135 setup_validation_autoencoder /
+ * setup_validation_diffusion, which run torch ops per batch and keep every prediction of the split on the host).
+ * sd_limb_stats (src/metrics/body_realism.py:4-107 limb_length_variance, limb_length_jitter, limb_length_error,
+ *   limb_length_variation_difference_wrtGT; the zero-hip padding of :7-10 is dead behind the assert of :6 and is
+ *   not reproduced): one read of pred (nseq, samples, frames, joints, 3); target (nseq, frames, joints, 3) or
+ *   NULL; f32, dense, 4-byte aligned (16-byte loads where the addresses allow).  limbseq (nlimbs, 2) is a HOST
+ *   int32 array, checked and passed to the kernel by value.  Limb lengths and all arithmetic on them are f64,
+ *   results f32.  Every output may be NULL and is then not computed.
+ *   limb_out (5, nseq, samples, nlimbs)   per limb, over the frames: 0 the unbiased variance of the length
+ *                               (torch.var, correction 1; NaN for frames == 1), 1 / 2 / 3 the mean / maximum /
+ *                               minimum of |len_t - len_{t-1}| over the frames - 1 steps (NaN for frames == 1),
+ *                               4 the mean of |target_len_t - len_t| (NaN without target)
+ *   sample_out (7, nseq, samples)         over the limbs: 0 / 1 / 2 mean / max / min of plane 0, 3 mean of plane 1,
+ *                               4 max of plane 2, 5 min of plane 3, 6 mean of plane 4
+ *   sample_scratch (7, nseq, samples) f64 the same in f64, workspace of seq_out
+ *   seq_out (9, nseq)                     over the samples: rows 0..6 reduce sample rows 0..6 each with its own
+ *                               operation (mean / max / min), rows 7 / 8 are the max / min of sample row 6
+ *   steps_out (nseq, samples, frames - 1, nlimbs)  |len_t - len_{t-1}| itself (limb_length_jitter mode 'none')
+ *   steps_diff_out (same shape)           that minus the target's |target_len_t - target_len_{t-1}|, subtracted in
+ *                               f64 (limb_length_variation_difference_wrtGT mode 'none'); needs target
+ *   The variance is Chan's combination, over the frame tiles in order, of per-tile sums of squares about the
+ *   tile's own mean: never E[x^2] - mean^2.  Maxima and minima keep a NaN, as torch.max / torch.min.  A limb's
+ *   sums run over the frames in frame order, a sample's reductions over the limbs in limb order, a sequence's
+ *   over the samples in sample order; no atomics.  The frame tile is sd_realism_frame_tile(joints).
+ *   1 <= samples, joints, nlimbs <= 64, frames >= 1, every limbseq entry in [0, joints), seq_out needs
+ *   sample_scratch (SD_E_INVALID names the argument, before any device call); nseq == 0 launches nothing.
+ * sd_frame_error_update (src/metrics/ignite_mpjpe.py MeanPerJointPositionError, src/metrics/ignite_fde.py
+ *   FinalDisplacementError: the streaming state of sum over the rows of the per-joint L2 distance):
+ *   pred (rows, samples, frames, joints, 3), target (rows, frames, joints, 3) f32, dense, 4-byte aligned;
+ *   idx (rows) DEVICE int64, the sample each row takes (sd_best_sample's idx_out: the chosen future is never
+ *   gathered), or NULL with samples == 1; the window is frames [frame0, frame0 + nframes) (the FDE: frame0 =
+ *   frames - 1, nframes = 1).  The state is updated in place:
+ *   sum (nframes, joints) f64   += over the rows ||pred[r, idx[r], frame0 + f, j, :] - target[r, frame0 + f, j, :]||
+ *                               (an f64 norm of f64 differences); each (frame, joint) adds its rows in ascending
+ *                               row order onto the value it holds, so the state after a dataset is bitwise the
+ *                               same however the rows were split into calls
+ *   count (1) int64             += rows
+ *   A row whose idx is outside [0, samples) adds NaN to all its sums and reads nothing of pred.  A NaN in pred
+ *   or target reaches only the (frame, joint) sums it belongs to.  One plain kernel, no atomics.
+ *   rows >= 0, 1 <= samples, joints <= 64, frames >= 1, 0 <= frame0 < frames, 1 <= nframes <= frames - frame0,
+ *   non-NULL sum and count (SD_E_INVALID names the argument, before any launch); rows == 0 launches nothing. */
+int sd_limb_stats(const float* pred, const float* target, int64_t nseq, int32_t samples, int32_t frames, int32_t joints,
+                  const int32_t* limbseq, int32_t nlimbs, float* limb_out, float* sample_out, double* sample_scratch,
+                  float* seq_out, float* steps_out, float* steps_diff_out, void* stream);
+int sd_frame_error_update(const float* pred, const float* target, const int64_t* idx, int64_t rows, int32_t samples,
+                          int32_t frames, int32_t joints, int32_t frame0, int32_t nframes, double* sum, int64_t* count,
+                          void* stream);
+
 /* Test hooks: one kernel on caller buffers, for the per-kernel numerics tests.
  * sd_test_graph_linear: out(B,J,N) = act(FiLM(ghat @ (s_j W[type j] [x1_j | x2_j] + bias[type j]))) + res,
  *   W (types,N,K1+K2), bias (types,N) or NULL, ghat (J,J), film (2N) or NULL, res (B,J,N) or NULL,

@@ -49,6 +49,7 @@ EXPORTED = (
     "sd_optim_workspace_bytes", "sd_optim_grad_norm", "sd_optim_adam_step", "sd_optim_ema_update",
     "sd_motion_batch", "sd_motion_draws", "sd_motion_batch_frame_tile",
     "sd_q_sample_groups",
+    "sd_limb_stats", "sd_frame_error_update",
 )
 
 # sd_plan_set_option keys (include/skeldiff.h)
@@ -220,6 +221,8 @@ def _declare(lib: ctypes.CDLL) -> None:
         "sd_motion_batch_frame_tile": (i32, [i32]),
         "sd_q_sample_groups": (ctypes.c_int, [vp, vp, vp, vp, vp, i32, i64, i32, i32, i32, vp, vp, u64, i64, i64, vp, vp,
                                               vp]),
+        "sd_limb_stats": (ctypes.c_int, [vp, vp, i64, i32, i32, i32, ctypes.POINTER(i32), i32, vp, vp, vp, vp, vp, vp, vp]),
+        "sd_frame_error_update": (ctypes.c_int, [vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp]),
         "sd_profile_step": (ctypes.c_int, [vp, vp, vp, i64, i32, i64, vp, sz, i32, ctypes.POINTER(ctypes.c_float),
                                            ctypes.POINTER(ctypes.c_int32), vp]),
     }

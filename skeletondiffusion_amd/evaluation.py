@@ -11,6 +11,8 @@ and the long-term rollouts (src/eval_utils.py:44-99), with the reference's signa
     get_fid_storer / get_apde_storer / get_cmd_storer   the dataset-level storers (config_metrics.py:55-69)
     metric_set(stats_mode, skeleton_key, ...)   all of them behind update / all_reduce / compute, the result table
                                              of an evaluation (config_metrics.py:71-96)
+    validation_set(kind, skeleton_key, loss_fn)   the validation table of the two training loops behind the same
+                                             three calls (src/train_utils.py:56-135 setup_validation_*)
 
 `model` is the (autoencoder, diffusion) pair of `prepare_model`.  Every stage is a HIP kernel sequence
 (sd_gru_encode, sd_sample_loop, sd_gru_decode, sd_best_sample); nothing here copies to the host or
@@ -272,6 +274,104 @@ def metric_set(stats_mode, skeleton_key, dataset_split="test", dataset_name="h36
     return MetricSet(stats, storers, extra)
 
 
+class _LossAccumulator:
+    """ignite.metrics.Loss: the batch-size-weighted mean of `loss_fn(y_pred, y)`; a float64 sum on the device of
+    the losses, the row count on the host (shapes are known without a copy)."""
+
+    def __init__(self, loss_fn):
+        self.loss_fn, self.sum, self.count = loss_fn, None, 0
+
+    def update(self, y_pred, y) -> None:
+        with torch.no_grad():
+            loss = self.loss_fn(y_pred, y)
+        if loss.dim() != 0:
+            raise ValueError("validation_set: loss_fn did not return the average loss")
+        term = loss.detach().to(torch.float64) * y.shape[0]
+        self.sum = term if self.sum is None else self.sum + term
+        self.count += int(y.shape[0])
+
+    def all_reduce(self, group=None):
+        import torch.distributed as dist
+
+        if self.sum is None:
+            raise metrics.SkelDiffError("validation_set: Loss.all_reduce before any update on this rank")
+        both = torch.stack([self.sum, torch.tensor(float(self.count), dtype=torch.float64, device=self.sum.device)])
+        dist.all_reduce(both, op=dist.ReduceOp.SUM, group=group)
+        self.sum, self.count = both[0], int(both[1])
+        return self
+
+    def compute(self) -> float:
+        if self.sum is None:
+            raise metrics.SkelDiffError("Loss must have at least one example before it can be computed.")
+        return float(self.sum.cpu()) / self.count
+
+
+class ValidationSet:
+    """What `validation_set` returns: `storers` maps the accumulated names of the validation table to their state."""
+
+    def __init__(self, kind, limbseq, loss_fn, device):
+        self.kind, self.limbseq = kind, limbseq
+        acc = partial(metrics.MetricAccumulator, "avg")
+        self.storers = {"MPJPE": metrics.MPJPEAccumulator(device=device)}
+        if kind == "autoencoder":
+            self.storers.update(ADE=acc(), FDE=metrics.FDEAccumulator(device=device))
+        else:
+            self.storers.update(APD=acc(), ADE=acc(), LLVar=acc())
+        if loss_fn is not None:
+            self.storers["Loss"] = _LossAccumulator(loss_fn)
+
+    def update(self, pred=None, target=None, pred_input=None, target_input=None, **kwargs) -> None:
+        """One validation batch in metric space: target (B, T, J, 3); pred (B, T, J, 3) for the autoencoder, (B, S,
+        T, J, 3) for the diffusion loop.  pred_input / target_input are the same pair in the model's input space,
+        for the loss (the diffusion loop's loss is taken on the sample closest to target_input,
+        train_utils.py:109).  Everything is queued on the current stream."""
+        st = self.storers
+        if self.kind == "autoencoder":
+            st["MPJPE"].update(pred, target)
+            st["ADE"].update(metrics.ade(pred=pred.unsqueeze(1), target=target))
+            st["FDE"].update(pred, target)
+        else:
+            st["MPJPE"].update(pred, target, best=True)  # the best sample, read where it lies
+            st["APD"].update(metrics.apd(pred=pred, target=target))
+            st["ADE"].update(metrics.ade(pred=pred, target=target))
+            st["LLVar"].update(metrics.limb_length_variance(pred=pred, limbseq=self.limbseq, mode="mean"))
+        if "Loss" in st:
+            if pred_input is None or target_input is None:
+                raise ValueError("validation_set: built with a loss_fn, update needs pred_input and target_input")
+            if self.kind == "diffusion":
+                pred_input, target_input = metrics.choose_best_sample(pred_input, target_input)
+            st["Loss"].update(pred_input, target_input)
+
+    def all_reduce(self, group=None) -> "ValidationSet":
+        for s in self.storers.values():
+            s.all_reduce(group)
+        return self
+
+    def compute(self) -> dict:
+        """The reference's `engine.state.metrics`: 'MPJPE' the time table (float64 host tensor), 'MPJPE_AVG' its
+        mean (train_utils.py:70-73), the other names Python floats."""
+        out = {}
+        for name, s in self.storers.items():
+            v = s.compute()
+            out[name] = v if name == "MPJPE" else float(v)
+            if name == "MPJPE":
+                out["MPJPE_AVG"] = v.mean(0)
+        return out
+
+
+def validation_set(kind, skeleton_key, loss_fn=None, device="cuda") -> ValidationSet:
+    """src/train_utils.py:56-95 `setup_validation_autoencoder` (kind 'autoencoder': MPJPE, MPJPE_AVG, ADE, FDE,
+    Loss) and :97-137 `setup_validation_diffusion` (kind 'diffusion': MPJPE of the best sample, MPJPE_AVG, APD, ADE,
+    LLVar, Loss) without ignite: `update(pred=, target=, pred_input=, target_input=)` per batch, `all_reduce()`
+    across ranks, `compute()` the table.  `loss_fn(y_pred, y)` is the model's loss (omitted from the table when
+    None).  No prediction is kept or copied to the host: the per-frame errors stream into float64 sums on the
+    device (sd_frame_error_update), the limb-length variance is one read of pred (sd_limb_stats)."""
+    if kind not in ("autoencoder", "diffusion"):
+        raise ValueError(f"validation_set: kind {kind!r} not supported, expected 'autoencoder' or 'diffusion'")
+    limbseq = skeletons.limbseq(skeleton_key) if kind == "diffusion" else None
+    return ValidationSet(kind, limbseq, loss_fn, device)
+
+
 __all__ = ["get_diffusion_latent_codes", "decode_latent_pred", "get_prediction", "process_evaluation_pair",
            "long_term_prediction_best_every50", "long_term_prediction_best_first50", "get_stats_funcs", "get_fid_storer",
-           "get_apde_storer", "get_cmd_storer", "metric_set", "MetricSet"]
+           "get_apde_storer", "get_cmd_storer", "metric_set", "MetricSet", "validation_set", "ValidationSet"]

@@ -35,6 +35,14 @@ reduction != 'mean'), reduced in a fixed order (deterministic).
                                       (sd_class_sum), update / merge / all_reduce / reset / motion_per_class / compute
     MetricAccumulator(return_op)      metric_storer.py       mean / max / min of per-sequence values, float64 on the device
 
+    limb_length_variance / limb_length_jitter(pred, limbseq, mode, if_per_sample), limb_length_error /
+    limb_length_variation_difference_wrtGT(target, pred, limbseq, mode)   body_realism.py:4-107
+    limb_stats(pred, limbseq, target)  all of them from one read of pred (sd_limb_stats)
+    format_metric_time_table(profile)  metrics/utils.py:5-10  frames 0, 30, 60, ... of a per-frame profile
+    MPJPEAccumulator / FDEAccumulator  ignite_mpjpe.py, ignite_fde.py  update / merge / all_reduce / reset / compute:
+                                      float64 sums per (frame, joint) on the device (sd_frame_error_update); the
+                                      best sample is read where it lies (`best=True` or `idx=`)
+
 Up to 64 samples per sequence (the release evaluation draws 50); up to 64 joints, limbs and angle pairs.
 
 cmd(val_per_frame, val_ref) (multimodal.py:10-13) is the one host-side function here: the CMD score of
@@ -376,6 +384,272 @@ def motion_for_cmd(pred: torch.Tensor) -> torch.Tensor:
     check(_lib.lib().sd_realism(p.data_ptr(), B, S, T, p.shape[3], limbs, 1, None, 0, gt_len.data_ptr(), None, None, T,
                                 *([None] * 8), scratch.data_ptr(), motion.data_ptr(), stream))
     return motion
+
+
+# ---- limb-length statistics of the validation pass (sd_limb_stats) ----------------------------------
+_LIMB_MODES = ("mean", "max", "min", "none")
+LimbStats = collections.namedtuple(
+    "LimbStats", ["variance_none"] + [f"variance_{m}{r}" for m in _LIMB_MODES[:3] for r in ("_persample", "")] +
+    ["jitter_none"] + [f"jitter_{m}{r}" for m in _LIMB_MODES[:3] for r in ("_limb", "_persample", "")] +
+    ["error_limb", "error_persample", "error_mean", "error_max", "error_min"])
+LimbStats.__doc__ = """What `limb_stats` returns.  variance_none (B, S, L) the unbiased variance of each limb's length over
+the frames; jitter_none (B, S, T - 1, L) the frame-to-frame change |len_t - len_{t-1}|; `{variance,jitter}_{mean,max,min}`
+with `_persample` (B, S): that reduction over the limbs (the jitter's also over the steps), and without a suffix (B,):
+the same reduction over the samples too; jitter_{mean,max,min}_limb (B, S, L) the reduction over the steps alone.
+error_limb (B, S, L) the mean over the frames of |target_len - len|, error_persample (B, S) its mean over the limbs,
+error_{mean,max,min} (B,) over the samples; the error fields are None without a target."""
+
+
+def _check_mode(mode, allowed, who):
+    if mode not in allowed:  # the reference asserts (body_realism.py:42, :56, :87)
+        raise ValueError(f"{who}: mode {mode!r} not supported, expected one of {list(allowed)}")
+
+
+def _limb_stats(pred, limbseq, target, want):
+    """One sd_limb_stats call computing the groups in `want` (a subset of 'limb', 'sample', 'seq', 'steps', 'diff');
+    -> dict of the raw output arrays (absent groups None) and the shape."""
+    p = _device_tensor(pred, "pred")
+    if p.dim() != 5 or p.shape[4] != 3:
+        raise ValueError(f"limb statistics: pred (B, S, T, J, 3) expected, got {tuple(p.shape)}")
+    B, S, T, J, _ = p.shape
+    g = None
+    if target is not None:
+        g = _device_tensor(target, "target")
+        if tuple(g.shape) != (B, T, J, 3):
+            raise ValueError(f"limb statistics: target {(B, T, J, 3)} expected for pred {tuple(p.shape)}, got {tuple(g.shape)}")
+    limbs, L = _int_table(limbseq, "limbseq")
+    dev = p.device
+    f32 = dict(device=dev, dtype=torch.float32)
+    o = {
+        "limb": torch.empty(5, B, S, L, **f32) if "limb" in want else None,
+        "sample": torch.empty(7, B, S, **f32) if "sample" in want else None,
+        "scratch": torch.empty(7, B, S, device=dev, dtype=torch.float64) if "seq" in want else None,
+        "seq": torch.empty(9, B, **f32) if "seq" in want else None,
+        "steps": torch.empty(B, S, T - 1, L, **f32) if "steps" in want else None,
+        "diff": torch.empty(B, S, T - 1, L, **f32) if "diff" in want else None,
+    }
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    check(_lib.lib().sd_limb_stats(p.data_ptr(), _lib.ptr(g), B, S, T, J, limbs, L, *(_lib.ptr(o[k]) for k in (
+        "limb", "sample", "scratch", "seq", "steps", "diff")), stream))
+    return o
+
+
+def limb_stats(pred: torch.Tensor, limbseq, target=None) -> LimbStats:
+    """Every limb-length statistic of the validation pass from one launch sequence and one read of pred
+    (B, S, T, J, 3); limbseq (L, 2) joint indices (`skeletons.limbseq`); target (B, T, J, 3) or None (then the
+    error fields are None).  Float64 inside; the variance over the frames is combined from per-tile sums of
+    squares about the tile's mean, never E[x^2] - mean^2.  -> `LimbStats`."""
+    o = _limb_stats(pred, limbseq, target, {"limb", "sample", "seq", "steps"})
+    lim, sam, seq = o["limb"], o["sample"], o["seq"]
+    var = [x for m in range(3) for x in (sam[m], seq[m])]
+    jit = [x for m in range(3) for x in (lim[1 + m], sam[3 + m], seq[3 + m])]
+    err = [lim[4], sam[6], seq[6], seq[7], seq[8]] if target is not None else [None] * 5
+    return LimbStats(lim[0], *var, o["steps"], *jit, *err)
+
+
+def _limb_mode(pred, limbseq, mode, if_per_sample, row0, who):
+    """`mode` over the limbs (and, without if_per_sample, over the samples) of the variance (row0 0) or jitter (row0 3)."""
+    _check_mode(mode, _LIMB_MODES, who)
+    m = _LIMB_MODES.index(mode)
+    if if_per_sample:
+        return _limb_stats(pred, limbseq, None, {"sample"})["sample"][row0 + m]
+    return _limb_stats(pred, limbseq, None, {"seq"})["seq"][row0 + m]
+
+
+def limb_length_variance(pred, limbseq, mode="mean", if_per_sample=False, **kwargs):
+    """body_realism.py:50-77: the unbiased variance over the frames of every limb's length, pred (B, S, T, J, 3):
+    mode 'none' (B, S, L); 'mean' / 'max' / 'min' over the limbs (B, S) with if_per_sample, else over the samples
+    too (B,).  The `LLVar` column of the diffusion loop's validation (train_utils.py:108).  T == 1 gives NaN."""
+    if mode == "none":
+        return _limb_stats(pred, limbseq, None, {"limb"})["limb"][0]
+    return _limb_mode(pred, limbseq, mode, if_per_sample, 0, "limb_length_variance")
+
+
+def limb_length_jitter(pred, limbseq, mode="mean", if_per_sample=False, **kwargs):
+    """body_realism.py:79-107: |len_t - len_{t-1}| of every limb: mode 'none' (B, S, T - 1, L); 'mean' / 'max' /
+    'min' over the limbs and steps (B, S) with if_per_sample, else over the samples too (B,).  'max' / 'min' of a
+    single frame have nothing to reduce (the reference's `max` over an empty axis raises): ValueError."""
+    _check_mode(mode, _LIMB_MODES, "limb_length_jitter")
+    if mode == "none":
+        return _limb_stats(pred, limbseq, None, {"steps"})["steps"]
+    if mode in ("max", "min") and pred.shape[2] < 2:
+        raise ValueError(f"limb_length_jitter: mode {mode!r} needs at least 2 frames, pred has {pred.shape[2]}")
+    return _limb_mode(pred, limbseq, mode, if_per_sample, 3, "limb_length_jitter")
+
+
+def limb_length_error(target, pred, limbseq, mode="mean", **kwargs):
+    """body_realism.py:32-48: the mean over limbs and frames of |target limb length - predicted limb length|,
+    then `mode` ('mean' / 'max' / 'min') over the samples -> (B,)."""
+    _check_mode(mode, _LIMB_MODES[:3], "limb_length_error")
+    return _limb_stats(pred, limbseq, target, {"seq"})["seq"][(6, 7, 8)[_LIMB_MODES.index(mode)]]
+
+
+def limb_length_variation_difference_wrtGT(target, pred, limbseq, mode="mean", **kwargs):
+    """body_realism.py:15-29: limb_length_jitter of the predictions minus that of the ground truth (as one
+    sample), both with `mode`, then the reference's own second reduction: over the last axis of the (B,) values,
+    i.e. over the batch, and `unsqueeze(0)` -> (1,); mode 'none' -> (B, S, T - 1, L).  `if_per_sample` is
+    limb_length_jitter's, as in the reference ((1, B) then).  The two jitters are subtracted in float64."""
+    _check_mode(mode, _LIMB_MODES, "limb_length_variation_difference_wrtGT")
+    if mode == "none":  # subtracted in float64 inside the kernel, rounded once
+        return _limb_stats(pred, limbseq, target, {"diff"})["diff"]
+    if mode in ("max", "min") and pred.shape[2] < 2:
+        raise ValueError(f"limb_length_variation_difference_wrtGT: mode {mode!r} needs at least 2 frames, pred has "
+                         f"{pred.shape[2]}")
+
+    def over_last(v):
+        return v.mean(-1) if mode == "mean" else (v.max(-1).values if mode == "max" else v.min(-1).values)
+
+    def jitter64(x):  # the kernel's float64 per-sample values, so the difference below is rounded once
+        v = _limb_stats(x, limbseq, None, {"seq"})["scratch"][3 + _LIMB_MODES.index(mode)]  # (B, S)
+        return v if kwargs.get("if_per_sample", False) else over_last(v)
+
+    p, g = jitter64(pred), jitter64(target.unsqueeze(1))
+    return (over_last(p) - over_last(g)).to(torch.float32).unsqueeze(0)
+
+
+# ---- streaming per-frame MPJPE and FDE (sd_frame_error_update, DESIGN.md §4ad) ---------------------------------------
+def format_metric_time_table(metric: torch.Tensor) -> torch.Tensor:
+    """metrics/utils.py:5-10: the rows 0, 30, 60, ... (at most 16) of a profile whose axis 0 is time."""
+    steps = [i * 30 for i in range(16) if i * 30 < len(metric)]
+    return torch.stack([metric[t] for t in steps], dim=0)
+
+
+class _FrameErrorAccumulator:
+    """State of the sum over the rows of ||pred - target|| per (frame, joint) of a frame window: float64 (nframes,
+    joints) and an int64 row count on `device`.  On a ROCm device `update` is one sd_frame_error_update launch
+    (after sd_best_sample for `best=True`); on the CPU (a state for `merge` / `all_reduce`, or a host validation)
+    the same row-ordered float64 sums are formed with torch ops."""
+
+    _name = "frame error"
+
+    def __init__(self, device=None):
+        self.device = torch.device(device or "cpu")
+        self.sum = None  # (nframes, J) once the first update gives the shape
+        self.count = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def reset(self) -> None:
+        self.sum = None
+        self.count.zero_()
+
+    def _window(self, frames: int):
+        raise NotImplementedError
+
+    def _state(self, nframes: int, joints: int) -> torch.Tensor:
+        if self.sum is None:
+            self.sum = torch.zeros(nframes, joints, dtype=torch.float64, device=self.device)
+        elif tuple(self.sum.shape) != (nframes, joints):
+            raise ValueError(f"{self._name}: a batch of {(nframes, joints)} (frames, joints) after batches of "
+                             f"{tuple(self.sum.shape)}")
+        return self.sum
+
+    def update(self, pred: torch.Tensor, target: torch.Tensor, idx=None, best: bool = False) -> None:
+        """pred (rows, frames, joints, 3) or (rows, samples, frames, joints, 3), target (rows, frames, joints, 3).
+        With several samples give `idx` (rows,) int64, the sample of every row (`metrics.best_sample`'s idx), or
+        `best=True`, which takes the sample closest to the target (sd_best_sample); the chosen future is read
+        where it lies.  Nothing is copied to the host."""
+        if not torch.is_tensor(pred) or not torch.is_tensor(target):
+            raise ValueError(f"{self._name}: pred and target must be tensors")
+        if pred.dim() == 4:
+            pred = pred.unsqueeze(1)
+        if pred.dim() != 5 or pred.shape[4] != 3 or target.dim() != 4 or \
+                tuple(target.shape) != (pred.shape[0],) + tuple(pred.shape[2:]):
+            raise ValueError(f"{self._name}: pred (rows, [samples,] frames, joints, 3) and target (rows, frames, joints, 3) "
+                             f"expected, got {tuple(pred.shape)} and {tuple(target.shape)}")
+        R, S, T, J, _ = pred.shape
+        if idx is not None and best:
+            raise ValueError(f"{self._name}: give idx or best=True, not both")
+        if idx is None and not best and S != 1:
+            raise ValueError(f"{self._name}: pred has {S} samples: give idx (rows,) or best=True")
+        frame0, nframes = self._window(T)
+        state = self._state(nframes, J)
+        if R == 0:
+            return
+        if self.device.type == "cuda":
+            p, g = _device_tensor(pred, "pred"), _device_tensor(target, "target")
+            if best:
+                idx = _best_sample(p, g, None, False, True, False)[2]
+            if idx is not None:
+                idx = torch.as_tensor(idx).to(device=p.device, dtype=torch.int64).reshape(-1).contiguous()
+                if idx.numel() != R:
+                    raise ValueError(f"{self._name}: {idx.numel()} indices for {R} rows")
+            stream = torch.cuda.current_stream(p.device).cuda_stream
+            check(_lib.lib().sd_frame_error_update(p.data_ptr(), g.data_ptr(), _lib.ptr(idx), R, S, T, J, frame0, nframes,
+                                                   state.data_ptr(), self.count.data_ptr(), stream))
+            return
+        p = pred.detach().to(self.device, torch.float32).to(torch.float64)
+        g = target.detach().to(self.device, torch.float32).to(torch.float64)
+        if best:
+            idx = (p - g.unsqueeze(1)).norm(dim=-1).mean(-1).mean(-1).min(dim=-1).indices
+        if idx is None:
+            idx = torch.zeros(R, dtype=torch.int64)
+        idx = torch.as_tensor(idx).to(device=self.device, dtype=torch.int64).reshape(-1)
+        if idx.numel() != R:
+            raise ValueError(f"{self._name}: {idx.numel()} indices for {R} rows")
+        ok = (idx >= 0) & (idx < S)
+        chosen = p[torch.arange(R), idx.clamp(0, S - 1), frame0:frame0 + nframes]
+        err = (chosen - g[:, frame0:frame0 + nframes]).norm(dim=-1)
+        err[~ok] = float("nan")  # the kernel's rule for an index that is no sample
+        for r in range(R):  # the kernel's order: the rows ascending
+            state += err[r]
+        self.count += R
+
+    def merge(self, other):
+        if other.sum is not None:
+            self._state(*other.sum.shape).add_(other.sum.to(self.device))
+        self.count += other.count.to(self.device)
+        return self
+
+    def all_reduce(self, group=None):
+        """Sum the states over the ranks; every rank must have seen a batch (the shape is the state's)."""
+        import torch.distributed as dist
+
+        if self.sum is None:
+            raise SkelDiffError(f"{self._name}: all_reduce before any update on this rank (the state's shape is unknown)")
+        dist.all_reduce(self.sum, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(self.count, op=dist.ReduceOp.SUM, group=group)
+        return self
+
+    def _mean(self) -> torch.Tensor:
+        """(nframes, joints) float64 on the host: the one copy"""
+        if self.sum is None:
+            raise SkelDiffError(f"{self._name} must have at least one example before it can be computed.")
+        flat = torch.cat([self.sum.reshape(-1), self.count.to(torch.float64)]).cpu()
+        return (flat[:-1] / flat[-1]).reshape(self.sum.shape)
+
+
+class MPJPEAccumulator(_FrameErrorAccumulator):
+    """The reference's `MeanPerJointPositionError` (src/metrics/ignite_mpjpe.py) without keeping the split's
+    predictions: `compute` is the mean over the rows of the per-joint distance, then over the joints unless
+    keep_joint_dim, then the time table (`format_metric_time_table`) with keep_time_dim, else the mean over the
+    frames: a float64 host tensor."""
+
+    _name = "MeanPerJointPositionError"
+
+    def __init__(self, keep_time_dim: bool = True, keep_joint_dim: bool = False, device=None):
+        super().__init__(device)
+        self.keep_time_dim, self.keep_joint_dim = keep_time_dim, keep_joint_dim
+
+    def _window(self, frames: int):
+        return 0, frames
+
+    def compute(self) -> torch.Tensor:
+        ret = self._mean()
+        if not self.keep_joint_dim:
+            ret = ret.mean(dim=-1)
+        return format_metric_time_table(ret) if self.keep_time_dim else ret.mean(0)
+
+
+class FDEAccumulator(_FrameErrorAccumulator):
+    """The reference's `FinalDisplacementError` (src/metrics/ignite_fde.py): the mean over rows and joints of the
+    last frame's per-joint distance, a 0-dim float64 host tensor."""
+
+    _name = "FinalDisplacementError"
+
+    def _window(self, frames: int):
+        return frames - 1, 1
+
+    def compute(self) -> torch.Tensor:
+        return self._mean().mean()
 
 
 # ---- FID (sd_fid_features + sd_fid_stats_update, DESIGN.md §4p) -----------------------------------------
@@ -886,4 +1160,6 @@ __all__ = ["lat_apd", "apd", "ade", "fde", "mmade", "mmfde", "cmd", "mpjpe", "be
            "choose_best_sample", "limb_stretching_normed_rmse", "limb_stretching_normed_mean", "limb_jitter_normed_rmse",
            "limb_jitter_normed_mean", "mae", "motion_for_cmd", "realism", "Realism", "FIDClassifier", "FIDAccumulator",
            "frechet_distance", "APDEAccumulator", "diverse_rank", "DiverseRank", "find_samples_maxapd_wrtGT",
-           "get_closest_and_nfurthest_maxapd", "CMDAccumulator", "MetricAccumulator"]
+           "get_closest_and_nfurthest_maxapd", "CMDAccumulator", "MetricAccumulator", "limb_length_variance",
+           "limb_length_jitter", "limb_length_error", "limb_length_variation_difference_wrtGT", "limb_stats", "LimbStats",
+           "format_metric_time_table", "MPJPEAccumulator", "FDEAccumulator"]
