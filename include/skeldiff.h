@@ -664,7 +664,8 @@ int sd_l1norm_rows_backward(const float* G, const float* dghat, float* dG, int32
  * Both need workspace >= sd_gru_train_workspace_bytes(rows, T, J, H, n_types).
  * Checked on the host before any device call (SD_E_INVALID names the argument): NULL pointers, J
  * outside 1..64, H not a positive multiple of 16 (at most 256), T < 1, Ta / Tg not in {1, T}, node
- * types out of range, a short workspace.  rows == 0: SD_OK (the backward zeroes dgx, dW_hh, db_hh). */
+ * types out of range, a short workspace, more than 262,140 rows in a backward asked for dgx.
+ * rows == 0: SD_OK (the backward zeroes dgx, dW_hh, db_hh). */
 size_t sd_gru_train_workspace_bytes(int64_t rows, int32_t T, int32_t J, int32_t H, int32_t n_types);
 int sd_gru_train_forward(const float* a, int32_t Ta, const float* h0, const float* gx, int32_t Tg, const float* W_hh,
                          const float* b_hh, const int64_t* node_types, int32_t n_types, int64_t rows, int32_t T,
@@ -683,6 +684,45 @@ int sd_gx_table_forward(const float* G, const float* G_add, int32_t J, int32_t T
                         float* gxt, void* stream);
 int sd_gx_table_backward(const float* G, const float* G_add, const float* gxt, const float* dgxt, int32_t J, int32_t T,
                          int32_t normalize0, float eps, float* dG, float* dG_add, void* stream);
+/* Training-side graph-LSTM: the recurrent core of StaticGraphLSTMCell.forward unrolled
+ * over a sequence by StaticGraphLSTM.forward / Decoder.forward (reference
+ * src/core/network/layers/recurrent.py:126-167 and :170-196, src/core/network/nn/encoder.py:55-82,
+ * src/core/network/nn/decoder.py:47-52 and :75-104, clockwork off) and the backward torch autograd
+ * derives for it.  Per step: P_t = a_t + W_hh h_{t-1} + b_hh (unmixed), Q_t = gx_t P_t in the chunk
+ * order i | f | g | o, s_t = sigma(Q_f) s_{t-1} + sigma(Q_i) tanh(Q_g), h_t = sigma(Q_o) tanh(s_t)
+ * (bias_ih takes no part, as in the reference).  Caller-owned device buffers, row-major f32:
+ *   a (rows, Ta, J, 4H) = W_ih x, unmixed, no bias; Ta = T (one projection per frame) or 1 (one
+ *   projection reused at every step), h0 and s0 (rows, J, H) the initial hidden and cell state,
+ *   gx (Tg, J, J) the mixing matrix per step, Tg = T or 1, W_hh (types, 4H, H), b_hh (types, 4H) or
+ *   NULL, node_types HOST int64 (J) with values in [0, n_types) (n_types = 0: shared weights,
+ *   W_hh (1, 4H, H), node_types ignored).
+ * sd_lstm_train_forward: hs (rows, T, J, H), the hidden state after each step, and s_last
+ *   (rows, J, H), the cell state after the last (NULL: not written).  With P (rows, T, J, 4H), gates
+ *   (rows, T, J, 4H) and sseq (rows, T, J, H) given (all three or none) it keeps the state backward
+ *   reads: P_t, [i | f | g | o] and s_t.
+ * sd_lstm_train_backward: from dhs (rows, T, J, H), that state and the forward's h0, s0, hs: da
+ *   (rows, Ta, J, 4H) (summed over the steps in order when Ta = 1), dh0, ds0 (rows, J, H), dgx
+ *   (Tg, J, J) (per step when Tg = T), dW_hh, db_hh; any output may be NULL (not computed).  Every
+ *   reduction over rows and steps runs in a fixed order (no float atomics): repeated calls give the
+ *   same bits.
+ * The backward needs workspace >= sd_lstm_train_workspace_bytes(rows, T, J, H, n_types); the forward
+ * only sd_lstm_train_forward_workspace_bytes(rows, J, H, n_types) (W_hh transposed, one step's P and two
+ * cell-state slabs: independent of T), which the former covers.
+ * Checked on the host before any device call (SD_E_INVALID names the argument): NULL pointers, J
+ * outside 1..64, H not a positive multiple of 16 (at most 256), T < 1, Ta / Tg not in {1, T}, node
+ * types out of range, a short workspace, more than 262,140 rows in a backward asked for dgx.
+ * rows == 0: SD_OK (the backward zeroes dgx, dW_hh, db_hh). */
+size_t sd_lstm_train_workspace_bytes(int64_t rows, int32_t T, int32_t J, int32_t H, int32_t n_types);
+size_t sd_lstm_train_forward_workspace_bytes(int64_t rows, int32_t J, int32_t H, int32_t n_types);
+int sd_lstm_train_forward(const float* a, int32_t Ta, const float* h0, const float* s0, const float* gx, int32_t Tg,
+                          const float* W_hh, const float* b_hh, const int64_t* node_types, int32_t n_types, int64_t rows,
+                          int32_t T, int32_t J, int32_t H, float* hs, float* s_last, float* P, float* gates, float* sseq,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int sd_lstm_train_backward(const float* dhs, int32_t Ta, const float* gx, int32_t Tg, const float* W_hh,
+                           const int64_t* node_types, int32_t n_types, const float* h0, const float* s0, const float* hs,
+                           const float* P, const float* gates, const float* sseq, int64_t rows, int32_t T, int32_t J,
+                           int32_t H, float* da, float* dh0, float* ds0, float* dgx, float* dW_hh, float* db_hh,
+                           void* workspace, size_t workspace_bytes, void* stream);
 /* PreNorm's RMSNorm under autograd (reference attention.py:30-36): x (R, C), R vectors of C
  * features, out = x / max(||x||, eps) * g * scale (scale = sqrt(C)); the forward also writes
  * dnorm (R) = max(||x||, eps) for the backward, which writes dx (R, C) and dg (C), the latter

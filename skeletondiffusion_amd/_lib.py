@@ -46,6 +46,8 @@ EXPORTED = (
     "sd_cdist", "sd_set_mean_distance", "sd_diverse_rank_workspace_bytes", "sd_diverse_rank", "sd_class_sum",
     "sd_gru_train_workspace_bytes", "sd_gru_train_forward", "sd_gru_train_backward", "sd_gx_table_forward",
     "sd_gx_table_backward",
+    "sd_lstm_train_workspace_bytes", "sd_lstm_train_forward_workspace_bytes", "sd_lstm_train_forward",
+    "sd_lstm_train_backward",
     "sd_optim_workspace_bytes", "sd_optim_grad_norm", "sd_optim_adam_step", "sd_optim_ema_update",
     "sd_motion_batch", "sd_motion_draws", "sd_motion_batch_frame_tile",
     "sd_q_sample_groups",
@@ -177,6 +179,12 @@ def _declare(lib: ctypes.CDLL) -> None:
                                                 vp, vp, vp, vp, vp, sz, vp]),
         "sd_gru_train_backward": (ctypes.c_int, [vp, vp, i32, vp, i32, vp, ctypes.POINTER(i64), i32, vp, vp, vp, i64, i32,
                                                  i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "sd_lstm_train_workspace_bytes": (sz, [i64, i32, i32, i32, i32]),
+        "sd_lstm_train_forward_workspace_bytes": (sz, [i64, i32, i32, i32]),
+        "sd_lstm_train_forward": (ctypes.c_int, [vp, i32, vp, vp, vp, i32, vp, vp, ctypes.POINTER(i64), i32, i64, i32, i32,
+                                                 i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "sd_lstm_train_backward": (ctypes.c_int, [vp, i32, vp, i32, vp, ctypes.POINTER(i64), i32, vp, vp, vp, vp, vp, vp,
+                                                  i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
         "sd_gx_table_forward": (ctypes.c_int, [vp, vp, i32, i32, i32, ctypes.c_float, vp, vp]),
         "sd_gx_table_backward": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, ctypes.c_float, vp, vp, vp]),
         "sd_attn_train_forward": (ctypes.c_int, [vp, vp, i64, i32, i32, i32, ctypes.c_float, vp]),

@@ -11,9 +11,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libskeldiff.so")
 SOURCES = ["sd_kernels.hip", "sd_graph_linear.hip", "sd_graph_linear_v3.hip", "sd_graph_linear_v4.hip", "sd_graph_linear_v5.hip",
-           "sd_metrics.hip", "sd_realism.hip", "sd_validation.hip", "sd_fid.hip", "sd_mmgt.hip", "sd_rank.hip", "sd_decoder.hip", "sd_train.hip", "sd_gru_train.hip",
+           "sd_metrics.hip", "sd_realism.hip", "sd_validation.hip", "sd_fid.hip", "sd_mmgt.hip", "sd_rank.hip", "sd_decoder.hip", "sd_train.hip", "sd_gru_train.hip", "sd_lstm_train.hip",
            "sd_optim.hip", "sd_motion_batch.hip", "sd_q_sample.hip", "sd_plan.hip"]
-HEADERS = ["sd_internal.h", "sd_device.h", "sd_gl4_args.h", "sd_gl4_lds.h", "sd_realism_addr.h", "sd_validation_addr.h", "sd_gru_gates.h", "sd_optim_math.h", "sd_optim_table.h",
+HEADERS = ["sd_internal.h", "sd_device.h", "sd_gl4_args.h", "sd_gl4_lds.h", "sd_realism_addr.h", "sd_validation_addr.h", "sd_gru_gates.h", "sd_lstm_gates.h", "sd_seq_train.h", "sd_optim_math.h", "sd_optim_table.h",
            "sd_philox.h", "sd_motion_batch_addr.h", "sd_q_sample_addr.h", "sd_ystore_map.h", "sd_workspace.h", "sd_rank_addr.h", "sd_store_policy.h",
            os.path.join("..", "..", "include", "skeldiff.h")]
 

@@ -10,6 +10,12 @@ state_dict keys as the reference, so its autoencoder checkpoints load strictly.
 module lives on a ROCm device; on the CPU they raise (no CPU evaluation path).  `forward` /
 `autoencode` (stage-1 training, autograd) run each GRU as one HIP sequence call per forward
 (`training.graph_gru` / `gx_table`) on a ROCm device and stay torch ops on the CPU.
+
+`recurrent_arch_enc` / `recurrent_arch_decoder` also take `StaticGraphLSTM` (`recurrent.py:13-203`,
+`encoder.py:55-75`, `decoder.py:47-52,75-78`): the cell keeps a cell state beside `h`, the module an
+`initial_hidden_c` layer.  Its sequences run on `training.graph_lstm` under the same conditions
+(DESIGN.md §4r2); `decode` / `get_past_embedding` of an LSTM side run the module's forward under
+`no_grad` (the HIP sequence forward on a ROCm device, torch ops on the CPU).
 """
 from __future__ import annotations
 
@@ -24,7 +30,8 @@ from torch.nn import Parameter
 from ... import training as _training
 from .layers import StaticGraphLinear
 
-__all__ = ["StaticGraphGRUCell", "StaticGraphGRU", "Encoder", "Decoder", "AutoEncoder"]
+__all__ = ["StaticGraphGRUCell", "StaticGraphGRU", "StaticGraphLSTMCell", "StaticGraphLSTM", "Encoder", "Decoder",
+           "AutoEncoder"]
 
 
 def _gmm(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
@@ -34,6 +41,8 @@ def _gmm(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
 
 class StaticGraphGRUCell(nn.Module):
     """recurrent.py:208-366 (the GRU cell; clockwork off -> the update mask is 1)."""
+
+    GATES = 3  # gate blocks stacked in weight_ih / weight_hh / the biases
 
     def __init__(self, input_size: int, hidden_size: int, num_nodes: Optional[int] = None, dropout: float = 0.,
                  recurrent_dropout: float = 0., graph_influence=None, learn_influence: bool = False,
@@ -72,18 +81,18 @@ class StaticGraphGRUCell(nn.Module):
         if node_types is not None:
             node_types = torch.as_tensor(node_types, dtype=torch.long)
             nt = int(node_types.max()) + 1
-            self.weight_ih = Parameter(torch.empty(nt, 3 * hidden_size, input_size))
-            self.weight_hh = Parameter(torch.empty(nt, 3 * hidden_size, hidden_size))
+            self.weight_ih = Parameter(torch.empty(nt, self.GATES * hidden_size, input_size))
+            self.weight_hh = Parameter(torch.empty(nt, self.GATES * hidden_size, hidden_size))
             self.register_buffer("node_type_index", node_types)
             lead = (nt,)
         else:
-            self.weight_ih = Parameter(torch.empty(3 * hidden_size, input_size))
-            self.weight_hh = Parameter(torch.empty(3 * hidden_size, hidden_size))
+            self.weight_ih = Parameter(torch.empty(self.GATES * hidden_size, input_size))
+            self.weight_hh = Parameter(torch.empty(self.GATES * hidden_size, hidden_size))
             self.register_buffer("node_type_index", None)
             lead = ()
         if bias:
-            self.bias_ih = Parameter(torch.empty(*lead, 3 * hidden_size))
-            self.bias_hh = Parameter(torch.empty(*lead, 3 * hidden_size))
+            self.bias_ih = Parameter(torch.empty(*lead, self.GATES * hidden_size))
+            self.bias_hh = Parameter(torch.empty(*lead, self.GATES * hidden_size))
         else:
             self.bias_ih = self.bias_hh = None
         self.clockwork = clockwork
@@ -96,7 +105,10 @@ class StaticGraphGRUCell(nn.Module):
         self.dropout = nn.Dropout(dropout)
         self.r_dropout = nn.Dropout(recurrent_dropout)
         self.num_nodes = num_nodes
-        stdv = 1.0 / math.sqrt(hidden_size)  # recurrent.py:310-318
+        self.init_weights()
+
+    def init_weights(self):
+        stdv = 1.0 / math.sqrt(self.hidden_size)  # recurrent.py:310-318
         for w in self.parameters():
             if w is self.G or w is self.G_add:
                 continue
@@ -135,16 +147,19 @@ class StaticGraphGRUCell(nn.Module):
 class StaticGraphGRU(nn.Module):
     """recurrent.py:369-391: stacked cells over the time axis of (B, T, N, D) inputs."""
 
+    CELL = StaticGraphGRUCell
+    EMPTY_STATE = (None, None)
+
     def __init__(self, input_size: int, hidden_size: int, num_layers: int = 1, layer_dropout: float = 0.0, **kwargs):
         super().__init__()
-        self.layers = nn.ModuleList([StaticGraphGRUCell(input_size, hidden_size, **kwargs)] +
-                                    [StaticGraphGRUCell(hidden_size, hidden_size, **kwargs)
+        self.layers = nn.ModuleList([self.CELL(input_size, hidden_size, **kwargs)] +
+                                    [self.CELL(hidden_size, hidden_size, **kwargs)
                                      for _ in range(num_layers - 1)])
         self.dropout = nn.Dropout(layer_dropout)
 
     def forward(self, input: torch.Tensor, states: Optional[List] = None, t_i: int = 0):
         if states is None:
-            states = [(None, None)] * len(self.layers)
+            states = [self.EMPTY_STATE] * len(self.layers)
         output_states = []
         output = input
         for i, layer in enumerate(self.layers):
@@ -156,6 +171,53 @@ class StaticGraphGRU(nn.Module):
             output = self.dropout(torch.stack(outs, dim=1))
             output_states.append(state)
         return output, output_states
+
+
+class StaticGraphLSTMCell(StaticGraphGRUCell):
+    """recurrent.py:13-167 (the LSTM cell; clockwork off -> the update mask is 1).  Same constructor
+    and parameters as the GRU cell with four gate blocks i | f | g | o; `bias_ih` is a parameter
+    and a state-dict key that the forward never reads, as in the reference."""
+
+    GATES = 4
+
+    def init_weights(self):
+        stdv = 1.0 / math.sqrt(self.hidden_size)  # recurrent.py:115-124
+        for w in self.parameters():
+            if w is self.G or w is self.G_add:
+                continue
+            w.data.uniform_(-stdv, stdv)
+            if w is self.weight_hh or (w is self.weight_ih and self.weight_ih.dim() == 3):
+                w.data[1:] = w.data[0]
+
+    def forward(self, input: torch.Tensor, state, t: int = 0):
+        hx, cx, gx = state
+        if hx is None:
+            hx = input.new_zeros(input.shape[0], self.num_nodes, self.hidden_size)
+        if cx is None:
+            cx = input.new_zeros(input.shape[0], self.num_nodes, self.hidden_size)
+        if gx is None:
+            gx = F.normalize(self.G, p=1., dim=1) if self.learn_influence else self.G
+        hx = self.r_dropout(hx)
+        w_ih, w_hh = self._typed(self.weight_ih), self._typed(self.weight_hh)
+        b_hh = self._typed(self.bias_hh) if self.bias_hh is not None else 0.
+        mm = _gmm if self.node_type_index is not None else torch.matmul
+        c_mask = (torch.remainder(torch.tensor(t + 1., device=input.device), self.phase) < 0.01).type_as(cx)
+        gates = self.dropout(mm(input, w_ih.transpose(-2, -1))) + mm(hx, w_hh.transpose(-2, -1)) + b_hh
+        i, f, g, o = torch.matmul(gx, gates).chunk(4, 2)
+        i, f, g, o = torch.sigmoid(i), torch.sigmoid(f), torch.tanh(g), torch.sigmoid(o)
+        cy = c_mask * (f * cx + i * g) + (1 - c_mask) * cx
+        hy = o * torch.tanh(cy)
+        gx = gx + self.G_add
+        if self.learn_influence or self.learn_additive_graph_influence:
+            gx = F.normalize(gx, p=1., dim=1)
+        return hy, (hy, cy, gx)
+
+
+class StaticGraphLSTM(StaticGraphGRU):
+    """recurrent.py:170-196: stacked LSTM cells over the time axis; states are (h, s, gx)."""
+
+    CELL = StaticGraphLSTMCell
+    EMPTY_STATE = (None, None, None)
 
 
 def _no_dropout(*mods) -> bool:
@@ -200,6 +262,14 @@ def _hip_gru_sequence(cell: StaticGraphGRUCell, x: torch.Tensor, h0: torch.Tenso
     nt = cell.node_type_index
     # unmixed input projections W_ih x + b_ih over all B Ta rows (identity mixing matrix)
     a = _training.graph_linear(x, cell.weight_ih, cell.bias_ih, eye, nt)
+    gx, gx_last = _hip_gx(cell, steps)
+    hs = _training.graph_gru(a, h0, gx, cell.weight_hh, cell.bias_hh, nt, steps=steps)
+    return hs, gx_last
+
+
+def _hip_gx(cell: StaticGraphGRUCell, steps: int):
+    """The cell's mixing matrices of `steps` steps, (Tg, J, J) with Tg = steps or 1, and the matrix
+    after the last step."""
     if isinstance(cell.G_add, torch.Tensor):
         table = _training.gx_table(cell.G, cell.G_add, steps + 1, normalize0=cell.learn_influence)
         gx, gx_last = table[:steps], table[steps]
@@ -211,14 +281,37 @@ def _hip_gru_sequence(cell: StaticGraphGRUCell, x: torch.Tensor, h0: torch.Tenso
         else:
             gx_last = F.normalize(cell.G, p=1., dim=1)
         gx = gx_last.unsqueeze(0)
-    hs = _training.graph_gru(a, h0, gx, cell.weight_hh, cell.bias_hh, nt, steps=steps)
-    return hs, gx_last
+    return gx, gx_last
+
+
+def _hip_lstm_sequence(cell: "StaticGraphLSTMCell", x: torch.Tensor, h0: torch.Tensor, s0: torch.Tensor, steps: int):
+    """The LSTM cell over `steps` steps on HIP (training.graph_lstm): x (B, Ta, J, D)
+    with Ta = steps or 1 -> hs (B, steps, J, H), the cell state and the mixing matrix after the
+    last step."""
+    dev = x.device
+    eye = getattr(cell, "_eye", None)
+    if eye is None or eye.device != dev:
+        eye = cell._eye = torch.eye(cell.num_nodes, device=dev, dtype=torch.float32)
+    nt = cell.node_type_index
+    # unmixed input projections W_ih x over all B Ta rows (identity mixing matrix; bias_ih is unused)
+    a = _training.graph_linear(x, cell.weight_ih, None, eye, nt)
+    gx, gx_last = _hip_gx(cell, steps)
+    hs, s_last = _training.graph_lstm(a, h0, s0, gx, cell.weight_hh, cell.bias_hh, nt, steps=steps)
+    return hs, s_last, gx_last
+
+
+_RECURRENT = {"StaticGraphGRU": StaticGraphGRU, "StaticGraphLSTM": StaticGraphLSTM}
 
 
 def _recurrent(arch: str):
-    if arch != "StaticGraphGRU":
-        raise NotImplementedError(f"recurrent arch {arch!r}: only StaticGraphGRU (the released configs) is built")
-    return StaticGraphGRU
+    if arch not in _RECURRENT:
+        raise NotImplementedError(f"recurrent arch {arch!r}: only StaticGraphGRU (the released configs) and "
+                                  "StaticGraphLSTM are built")
+    return _RECURRENT[arch]
+
+
+def _is_lstm(arch: str) -> bool:
+    return arch == "StaticGraphLSTM"
 
 
 class Encoder(nn.Module):
@@ -239,10 +332,24 @@ class Encoder(nn.Module):
                                     bias=True, learn_influence=True)
         self.initial_hidden1 = StaticGraphLinear(input_size, hidden_size, num_nodes=num_nodes,
                                                  node_types=node_types, bias=True, learn_influence=True)
+        if _is_lstm(recurrent_arch):  # encoder.py:55-61
+            self.initial_hidden_c = StaticGraphLinear(input_size, hidden_size, num_nodes=num_nodes,
+                                                      node_types=node_types, bias=True, learn_influence=True)
         self.dropout = nn.Dropout(dropout)
 
     def forward(self, x: torch.Tensor, state=None):
-        if state is None and x.dim() == 4 and x.shape[1] >= 1 and _hip_sequence_ok(self.rnn, x, self.dropout):
+        hip = state is None and x.dim() == 4 and x.shape[1] >= 1 and _hip_sequence_ok(self.rnn, x, self.dropout)
+        if _is_lstm(self.recurrent_arch):
+            if hip:  # the whole sequence in one HIP call (forward + BPTT)
+                hs, s_last, gx = _hip_lstm_sequence(self.rnn.layers[0], x, _hip_linear(self.initial_hidden1, x[:, 0]),
+                                                    _hip_linear(self.initial_hidden_c, x[:, 0]), x.shape[1])
+                h_last = hs[:, -1]
+                return self.activation_fn(_hip_linear(self.fc, h_last)), [(h_last, s_last, gx)]
+            if state is None:  # encoder.py:64-75
+                state = [(self.initial_hidden1(x[:, 0]), self.initial_hidden_c(x[:, 0]), None)] * self.num_layers
+            y, state = self.rnn(input=x, states=state)
+            return self.activation_fn(self.fc(self.dropout(y[:, -1]))), state
+        if hip:
             # the whole sequence in one HIP call (forward + BPTT)
             hs, gx = _hip_gru_sequence(self.rnn.layers[0], x, _hip_linear(self.initial_hidden1, x[:, 0]), x.shape[1])
             h_last = hs[:, -1]
@@ -271,6 +378,9 @@ class Decoder(nn.Module):
                                                       learn_additive_graph_influence=True, clockwork=False)
         self.initial_hidden_h = StaticGraphLinear(feature_size + input_size, hidden_size, num_nodes=num_nodes,
                                                   learn_influence=True, node_types=node_types)
+        if _is_lstm(recurrent_arch_decoder):  # decoder.py:47-52
+            self.initial_hidden_c = StaticGraphLinear(feature_size + input_size, hidden_size, num_nodes=num_nodes,
+                                                      learn_influence=True, node_types=node_types)
         self.fc = StaticGraphLinear(hidden_size, output_size, num_nodes=num_nodes, learn_influence=True,
                                     node_types=node_types)
         self.dropout = nn.Dropout(dropout)
@@ -278,8 +388,13 @@ class Decoder(nn.Module):
     def init_recurrent_hidden(self, x, h, z, state=None):
         x_t = x[:, -1]
         x_t_1 = x[:, -2] if state is None else state
-        rnn_h = self.initial_hidden_h(torch.cat([x_t_1, h], dim=-1))
-        return torch.cat([x_t, h], dim=-1).unsqueeze(1), [(rnn_h, None)] * self.num_layers
+        init = torch.cat([x_t_1, h], dim=-1)
+        rnn_h = self.initial_hidden_h(init)
+        if _is_lstm(self.recurrent_arch):  # decoder.py:75-78
+            hidden = [(rnn_h, self.initial_hidden_c(init), None)] * self.num_layers
+        else:
+            hidden = [(rnn_h, None)] * self.num_layers
+        return torch.cat([x_t, h], dim=-1).unsqueeze(1), hidden
 
     def forward(self, x: torch.Tensor, h: torch.Tensor, z: torch.Tensor, ph: int = 1, state=None):
         """Training forward (autograd): one HIP sequence call on a ROCm device, torch ops
@@ -287,9 +402,14 @@ class Decoder(nn.Module):
         x_t_s = x[:, -1].clone()
         if ph >= 1 and _hip_sequence_ok(self.rnn, x, self.dropout):
             x_t_1 = x[:, -2] if state is None else state
-            rnn_h = _hip_linear(self.initial_hidden_h, torch.cat([x_t_1, h], dim=-1))
+            init = torch.cat([x_t_1, h], dim=-1)
+            rnn_h = _hip_linear(self.initial_hidden_h, init)
             rec_input = torch.cat([x[:, -1], h], dim=-1).unsqueeze(1)  # the same input at every step
-            hs, _ = _hip_gru_sequence(self.rnn.layers[0], rec_input, rnn_h, ph)
+            if _is_lstm(self.recurrent_arch):
+                hs = _hip_lstm_sequence(self.rnn.layers[0], rec_input, rnn_h, _hip_linear(self.initial_hidden_c, init),
+                                        ph)[0]
+            else:
+                hs, _ = _hip_gru_sequence(self.rnn.layers[0], rec_input, rnn_h, ph)
             return self.activation_fn(_hip_linear(self.fc, hs)), x_t_s  # fc over all ph states at once
         rec_input, hidden = self.init_recurrent_hidden(x=x, h=h, z=z, state=state)
         out = []
@@ -338,6 +458,11 @@ class AutoEncoder(nn.Module):
         eval_prepare_model.py:89-99); no_grad as the reference."""
         if state is not None:
             raise NotImplementedError("get_past_embedding(state=...) is not used by the evaluation and not built")
+        if _is_lstm(self.encoder.recurrent_arch):
+            # no LSTM engine: the module's own forward under no_grad (the HIP sequence forward on a
+            # ROCm device, torch ops on the CPU)
+            with torch.no_grad():
+                return self.z_activation(self(past))
         return self._hip().encode(past)
 
     def get_embedding(self, future, state=None):
@@ -351,6 +476,9 @@ class AutoEncoder(nn.Module):
         (decoder.py:85-104 semantics; `z` is unused there too)."""
         if state is not None:
             raise NotImplementedError("decode(state=...) is not used by the evaluation and not built")
+        if _is_lstm(self.decoder.recurrent_arch):
+            with torch.no_grad():
+                return self.decoder(x=x[:, -2:], h=h, z=z, ph=ph)[0]
         return self._hip().decode(x[:, -2:], h, ph)
 
     def autoencode(self, y, past, ph=1, state=None):

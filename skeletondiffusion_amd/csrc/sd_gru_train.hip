@@ -11,7 +11,7 @@
 //                       k_gru_bwd_hh (dc_t = gx_t^T dHh_t, dh_{t-1} = carry + W_hh^T dc_t)
 //   after the reverse sweep, over all B T rows at once: da = gx^T dX (k_gru_da), dW_hh / db_hh
 //   (the per-type GEMM and bias reduction of sd_gl_train_backward on x = h_{t-1}, dy = dc with an
-//   identity mixing matrix), dgx = sum_b (dX a^T + dHh c^T) (k_gru_dgx_part + k_gru_dgx_sum).
+//   identity mixing matrix), dgx = sum_b (dX a^T + dHh c^T) (k_gru_dgx_part + k_seq_dgx_sum).
 // Every reduction over rows and steps runs in a fixed order (no float atomics): two runs give
 // the same bits.  The gate math is sd_gru_gates.h, shared with the host emulation.
 #include <hip/hip_runtime.h>
@@ -26,24 +26,12 @@
 namespace sd {
 namespace {
 
-constexpr int kGruMaxH = 256;   // hidden width the per-step kernels' LDS tiles are sized for
-constexpr int kGruRT = 8;       // rows per workgroup of k_gru_hh / k_gru_bwd_hh
-constexpr int kGruCH = 16;      // hidden features per workgroup of k_gru_gate (H % 16 == 0)
-constexpr int kGruDgxRows = 4;  // rows per partial of the dgx reduction
+#include "sd_seq_train.h"
 
-struct NodeTypes {
-    int t[kMaxNodes];
-};
-
-__global__ void k_gru_write_types(NodeTypes nt, int J, int64_t* __restrict__ out) {
-    const int j = threadIdx.x;
-    if (j < J) out[j] = nt.t[j];
-}
-
-__global__ void k_gru_identity(float* __restrict__ I, int J) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < J * J) I[k] = (k / J == k % J) ? 1.f : 0.f;
-}
+constexpr int kGruMaxH = kSeqMaxH;        // hidden width the per-step kernels' LDS tiles are sized for
+constexpr int kGruRT = kSeqRT;            // rows per workgroup of k_gru_hh / k_gru_bwd_hh
+constexpr int kGruCH = 16;                // hidden features per workgroup of k_gru_gate (H % 16 == 0)
+constexpr int kGruDgxRows = kSeqDgxRows;  // rows per partial of the dgx reduction
 
 // W (types, 3H, H) -> Wt (types, H, 3H): k_gru_hh reads unit-stride over the output column
 __global__ void k_gru_transpose_w(const float* __restrict__ W, int64_t types, int H, float* __restrict__ Wt) {
@@ -337,23 +325,6 @@ __global__ __launch_bounds__(256) void k_gru_dgx_part(const float* __restrict__ 
         }
 }
 
-// dgx[g][e] = sum of `cnt` partials from part[g * cnt]: one wave per element, lane l takes the
-// partials l, l + 64, ... in order, then a fixed xor-shuffle tree
-__global__ __launch_bounds__(256) void k_gru_dgx_sum(const float* __restrict__ part, int cnt, int JJ, int64_t total,
-                                                     float* __restrict__ out) {
-    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (w >= total) return;  // wave-uniform
-    const int l = threadIdx.x & 63;
-    const int64_t g = w / JJ;
-    const int e = (int)(w % JJ);
-    const float* p = part + g * cnt * JJ + e;
-    float acc = 0.f;
-    for (int s = l; s < cnt; s += 64) acc += p[(int64_t)s * JJ];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if (l == 0) out[w] = acc;
-}
-
 __device__ __forceinline__ float wave_sum64(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -445,31 +416,6 @@ size_t gru_carve(int64_t B, int T, int J, int H, int n_types, char* base, GruWS*
     return off > fwd ? off : fwd;
 }
 
-// shared argument checks of the three core entries; returns SD_OK or sets the error
-int gru_check(const char* fn, int64_t rows, int T, int Ta, int Tg, int J, int H, const int64_t* node_types, int n_types,
-              NodeTypes* nt) {
-    const std::string f(fn);
-    if (rows < 0) return set_error(SD_E_INVALID, f + ": rows < 0");
-    if (T < 1) return set_error(SD_E_INVALID, f + ": T must be >= 1");
-    if (J < 1 || J > kMaxNodes) return set_error(SD_E_INVALID, f + ": J outside 1..64");
-    if (H < 16 || H % 16 != 0 || H > kGruMaxH)
-        return set_error(SD_E_INVALID, f + ": H must be a positive multiple of 16, at most 256");
-    if (Ta != 1 && Ta != T) return set_error(SD_E_INVALID, f + ": Ta must be 1 or T");
-    if (Tg != 1 && Tg != T) return set_error(SD_E_INVALID, f + ": Tg must be 1 or T");
-    if (n_types < 0) return set_error(SD_E_INVALID, f + ": n_types < 0");
-    if (n_types > 0 && !node_types) return set_error(SD_E_INVALID, f + ": node_types is null with n_types > 0");
-    for (int j = 0; j < kMaxNodes; ++j) nt->t[j] = 0;
-    if (n_types > 0)
-        for (int j = 0; j < J; ++j) {
-            if (node_types[j] < 0 || node_types[j] >= n_types)
-                return set_error(SD_E_INVALID, f + ": node_types[" + std::to_string(j) + "] out of range");
-            nt->t[j] = (int)node_types[j];
-        }
-    if (rows * (int64_t)T > INT32_MAX / 2 || (rows + kGruRT - 1) / kGruRT > 65535)
-        return set_error(SD_E_INVALID, f + ": too many rows");
-    return SD_OK;
-}
-
 }  // namespace
 }  // namespace sd
 
@@ -485,7 +431,7 @@ int sd_gru_train_forward(const float* a, int32_t Ta, const float* h0, const floa
                          int32_t J, int32_t H, float* hs, float* hprev, float* c, float* gates, void* workspace,
                          size_t workspace_bytes, void* stream) {
     sd::NodeTypes nt;
-    if (int rc = sd::gru_check("sd_gru_train_forward", rows, T, Ta, Tg, J, H, node_types, n_types, &nt)) return rc;
+    if (int rc = sd::seq_check("sd_gru_train_forward", rows, T, Ta, Tg, J, H, node_types, n_types, false, &nt)) return rc;
     const bool keep = hprev || c || gates;
     if (keep && !(hprev && c && gates))
         return sd::set_error(SD_E_INVALID, "sd_gru_train_forward: hprev, c and gates are kept together (all or none)");
@@ -537,7 +483,7 @@ int sd_gru_train_backward(const float* dhs, const float* a, int32_t Ta, const fl
                           const float* gates, int64_t rows, int32_t T, int32_t J, int32_t H, float* da, float* dh0,
                           float* dgx, float* dW_hh, float* db_hh, void* workspace, size_t workspace_bytes, void* stream) {
     sd::NodeTypes nt;
-    if (int rc = sd::gru_check("sd_gru_train_backward", rows, T, Ta, Tg, J, H, node_types, n_types, &nt)) return rc;
+    if (int rc = sd::seq_check("sd_gru_train_backward", rows, T, Ta, Tg, J, H, node_types, n_types, dgx != nullptr, &nt)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int types = n_types > 0 ? n_types : 1;
     const int H3 = 3 * H;
@@ -588,17 +534,17 @@ int sd_gru_train_backward(const float* dhs, const float* a, int32_t Ta, const fl
         SD_HIP(hipGetLastError());
         const int cnt = (Tg == 1 ? T : 1) * chunks;
         const int64_t total = (int64_t)Tg * J * J;
-        hipLaunchKernelGGL(sd::k_gru_dgx_sum, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, s, w.part, cnt, J * J, total,
+        hipLaunchKernelGGL(sd::k_seq_dgx_sum, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, s, w.part, cnt, J * J, total,
                            dgx);
         SD_HIP(hipGetLastError());
     }
     if (dW_hh || db_hh) {
         // dW_hh = sum_{b,t} dc (x) h_{t-1}, db_hh = sum_{b,t} dc: the graph-linear's weight / bias
         // gradient over B T rows with an identity mixing matrix (one pass, fixed order)
-        hipLaunchKernelGGL(sd::k_gru_identity, dim3((unsigned)((J * J + 255) / 256)), dim3(256), 0, s, w.ident, J);
+        hipLaunchKernelGGL(sd::k_seq_identity, dim3((unsigned)((J * J + 255) / 256)), dim3(256), 0, s, w.ident, J);
         SD_HIP(hipGetLastError());
         if (n_types > 0) {
-            hipLaunchKernelGGL(sd::k_gru_write_types, dim3(1), dim3(64), 0, s, nt, J, w.types);
+            hipLaunchKernelGGL(sd::k_seq_write_types, dim3(1), dim3(64), 0, s, nt, J, w.types);
             SD_HIP(hipGetLastError());
         }
         // (z feeds only dghat, which is not asked for; the entry still wants a non-null pointer)

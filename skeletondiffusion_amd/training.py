@@ -16,6 +16,8 @@ tensor, grad is enabled and `hip_training_enabled()`; there is no silent CPU fal
 `graph_gru` / `gx_table` are the graph-GRU sequence core and its per-step mixing matrices for
 stage-1 training of the motion autoencoder (`sd_gru_train_*`, `sd_gx_table_*`,
 csrc/sd_gru_train.hip), under the same switch.
+`graph_lstm` is the same for StaticGraphLSTM encoders / decoders (`sd_lstm_train_*`,
+csrc/sd_lstm_train.hip).
 
 `hip_forward_only()` lets the same forward kernels serve a forward under `no_grad`, and
 `q_sample_groups` is the forward process for k noisy copies per sequence (`sd_q_sample_groups`,
@@ -243,6 +245,9 @@ def graph_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Ten
 # launches of the sequence entries since import, by name (tests and tools read it as a spy)
 CALLS = collections.Counter()
 
+# forwards of the sequence cores that kept their backward's state, by cell ("gru", "lstm")
+STATE_KEPT = collections.Counter()
+
 GRU_MAX_HIDDEN = 256  # sd_gru_train_*: H a positive multiple of 16, at most 256
 
 
@@ -267,13 +272,20 @@ def _host_types(node_types, J: int):
 _HOST_TYPES: dict = {}
 
 
+def _keeps_state(*tensors) -> bool:
+    """Whether a sequence forward keeps the state its backward reads: grad mode is on and an input
+    asks for a gradient.  Decided outside the Function: inside its forward, `ctx.needs_input_grad`
+    is True for every `requires_grad` input (the Parameters) under `no_grad` too."""
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
 class GraphGRUFunction(torch.autograd.Function):
     """hs = the StaticGraphGRU cell unrolled over T steps from the unmixed input projections
     (`sd_gru_train_forward` / `_backward`, csrc/sd_gru_train.hip).  The state backward reads is
-    kept only when an input needs a gradient (under no_grad the same forward runs without it)."""
+    kept only when `keep` (`_keeps_state`: under no_grad the same forward runs without it)."""
 
     @staticmethod
-    def forward(ctx, a, h0, gx, weight_hh, bias_hh, node_types, T: int):
+    def forward(ctx, a, h0, gx, weight_hh, bias_hh, node_types, T: int, keep: bool):
         B, Ta, J, H3 = a.shape
         H = H3 // 3
         Tg = gx.shape[0]
@@ -283,7 +295,6 @@ class GraphGRUFunction(torch.autograd.Function):
         b2 = None if bias_hh is None else bias_hh.reshape(w3.shape[0], H3).contiguous()
         nt = _host_types(node_types, J)
         dev = a.device
-        keep = any(ctx.needs_input_grad[:5])
         hs = torch.empty(B, T, J, H, device=dev, dtype=torch.float32)
         hprev = torch.empty_like(hs) if keep else None
         c = torch.empty(B, T, J, H3, device=dev, dtype=torch.float32) if keep else None
@@ -292,6 +303,7 @@ class GraphGRUFunction(torch.autograd.Function):
         ws_bytes = L.sd_gru_train_workspace_bytes(B, T, J, H, n_types)
         ws = torch.empty(max(1, (ws_bytes + 3) // 4), device=dev, dtype=torch.float32)
         CALLS["gru_forward"] += 1
+        STATE_KEPT["gru"] += int(keep)
         _lib.check(L.sd_gru_train_forward(
             ac.data_ptr(), Ta, hc.data_ptr(), gc.data_ptr(), Tg, w3.data_ptr(), _lib.ptr(b2), nt, n_types, B, T, J, H,
             hs.data_ptr(), _lib.ptr(hprev), _lib.ptr(c), _lib.ptr(gates), ws.data_ptr(), ws_bytes, _stream(dev)))
@@ -323,7 +335,7 @@ class GraphGRUFunction(torch.autograd.Function):
             _lib.ptr(db), ws.data_ptr(), ws_bytes, _stream(dev)))
         return (None if da is None else da.reshape(ashape), None if dh0 is None else dh0.reshape(hshape),
                 None if dgx is None else dgx.reshape(gshape), None if dW is None else dW.reshape(wshape),
-                None if db is None else db.reshape(bshape), None, None)
+                None if db is None else db.reshape(bshape), None, None, None)
 
 
 def graph_gru(a: torch.Tensor, h0: torch.Tensor, gx: torch.Tensor, weight_hh: torch.Tensor,
@@ -350,7 +362,110 @@ def graph_gru(a: torch.Tensor, h0: torch.Tensor, gx: torch.Tensor, weight_hh: to
         raise ValueError("graph_gru: weight_hh (types, 3H, H) with node_types, or (3H, H) without")
     if bias_hh is not None and bias_hh.numel() != weight_hh.numel() // H:
         raise ValueError("graph_gru: bias_hh must hold 3H values per weight type")
-    return GraphGRUFunction.apply(a, h0, gx, weight_hh, bias_hh, node_types, T)
+    return GraphGRUFunction.apply(a, h0, gx, weight_hh, bias_hh, node_types, T,
+                                  _keeps_state(a, h0, gx, weight_hh, bias_hh))
+
+
+# ---- graph-LSTM sequence core (reference recurrent.py:126-196) --------------------
+
+# launches of the LSTM sequence entries since import, by name (a counter of its own: CALLS holds
+# the GRU path's names only)
+LSTM_CALLS = collections.Counter()
+
+LSTM_MAX_HIDDEN = 256  # sd_lstm_train_*: H a positive multiple of 16, at most 256
+
+
+class GraphLSTMFunction(torch.autograd.Function):
+    """(hs, s_last) = the StaticGraphLSTM cell unrolled over T steps from the unmixed input
+    projections (`sd_lstm_train_forward` / `_backward`, csrc/sd_lstm_train.hip).  The state backward
+    reads is kept only when `keep` (`_keeps_state`); without it the same forward runs, allocates
+    neither P, gates nor the cell states, and takes the forward-only workspace.  s_last is not
+    differentiable."""
+
+    @staticmethod
+    def forward(ctx, a, h0, s0, gx, weight_hh, bias_hh, node_types, T: int, keep: bool):
+        B, Ta, J, H4 = a.shape
+        H = H4 // 4
+        Tg = gx.shape[0]
+        ac, hc, sc, gc = a.contiguous(), h0.contiguous(), s0.contiguous(), gx.contiguous()
+        w3 = (weight_hh if weight_hh.dim() == 3 else weight_hh.unsqueeze(0)).contiguous()
+        n_types = int(w3.shape[0]) if node_types is not None else 0
+        b2 = None if bias_hh is None else bias_hh.reshape(w3.shape[0], H4).contiguous()
+        nt = _host_types(node_types, J)
+        dev = a.device
+        hs = torch.empty(B, T, J, H, device=dev, dtype=torch.float32)
+        s_last = torch.empty(B, J, H, device=dev, dtype=torch.float32)
+        P = torch.empty(B, T, J, H4, device=dev, dtype=torch.float32) if keep else None
+        gates = torch.empty(B, T, J, H4, device=dev, dtype=torch.float32) if keep else None
+        sseq = torch.empty(B, T, J, H, device=dev, dtype=torch.float32) if keep else None
+        L = _lib.lib()
+        ws_bytes = L.sd_lstm_train_forward_workspace_bytes(B, J, H, n_types)
+        ws = torch.empty(max(1, (ws_bytes + 3) // 4), device=dev, dtype=torch.float32)
+        LSTM_CALLS["lstm_forward"] += 1
+        STATE_KEPT["lstm"] += int(keep)
+        _lib.check(L.sd_lstm_train_forward(
+            ac.data_ptr(), Ta, hc.data_ptr(), sc.data_ptr(), gc.data_ptr(), Tg, w3.data_ptr(), _lib.ptr(b2), nt, n_types,
+            B, T, J, H, hs.data_ptr(), s_last.data_ptr(), _lib.ptr(P), _lib.ptr(gates), _lib.ptr(sseq), ws.data_ptr(),
+            ws_bytes, _stream(dev)))
+        if keep:
+            ctx.save_for_backward(gc, w3, hc, sc, hs, P, gates, sseq)
+            ctx.meta = (B, T, Ta, Tg, J, H, n_types, nt, weight_hh.shape, None if bias_hh is None else bias_hh.shape,
+                        a.shape, h0.shape, gx.shape)
+        ctx.mark_non_differentiable(s_last)
+        return hs, s_last
+
+    @staticmethod
+    def backward(ctx, dhs, _ds_last):
+        gc, w3, hc, sc, hs, P, gates, sseq = ctx.saved_tensors
+        B, T, Ta, Tg, J, H, n_types, nt, wshape, bshape, ashape, hshape, gshape = ctx.meta
+        need_a, need_h, need_s, need_g, need_w, need_b = ctx.needs_input_grad[:6]
+        dev = gc.device
+        dc = dhs.contiguous().float()
+        da = torch.empty(B, Ta, J, 4 * H, device=dev) if need_a else None
+        dh0 = torch.empty(B, J, H, device=dev) if need_h else None
+        ds0 = torch.empty(B, J, H, device=dev) if need_s else None
+        dgx = torch.empty(Tg, J, J, device=dev) if need_g else None
+        dW = torch.empty(w3.shape, device=dev) if need_w else None
+        db = torch.empty(w3.shape[0], 4 * H, device=dev) if (need_b and bshape is not None) else None
+        L = _lib.lib()
+        ws_bytes = L.sd_lstm_train_workspace_bytes(B, T, J, H, n_types)
+        ws = torch.empty(max(1, (ws_bytes + 3) // 4), device=dev, dtype=torch.float32)
+        LSTM_CALLS["lstm_backward"] += 1
+        _lib.check(L.sd_lstm_train_backward(
+            dc.data_ptr(), Ta, gc.data_ptr(), Tg, w3.data_ptr(), nt, n_types, hc.data_ptr(), sc.data_ptr(),
+            hs.data_ptr(), P.data_ptr(), gates.data_ptr(), sseq.data_ptr(), B, T, J, H, _lib.ptr(da), _lib.ptr(dh0),
+            _lib.ptr(ds0), _lib.ptr(dgx), _lib.ptr(dW), _lib.ptr(db), ws.data_ptr(), ws_bytes, _stream(dev)))
+        return (None if da is None else da.reshape(ashape), None if dh0 is None else dh0.reshape(hshape),
+                None if ds0 is None else ds0.reshape(hshape), None if dgx is None else dgx.reshape(gshape),
+                None if dW is None else dW.reshape(wshape), None if db is None else db.reshape(bshape), None, None, None)
+
+
+def graph_lstm(a: torch.Tensor, h0: torch.Tensor, s0: torch.Tensor, gx: torch.Tensor, weight_hh: torch.Tensor,
+               bias_hh: Optional[torch.Tensor], node_types: Optional[torch.Tensor], steps: Optional[int] = None):
+    """HIP graph-LSTM core under autograd (fp32 device tensors; recurrent.py:126-167 unrolled,
+    clockwork off).  a (B, Ta, J, 4H) = the unmixed input projections W_ih x (no bias: the cell never
+    reads bias_ih), Ta = T or 1 (one projection reused at every step); h0, s0 (B, J, H) the initial
+    hidden and cell state; gx (Tg, J, J) or (J, J), Tg = T or 1; weight_hh (types, 4H, H) with
+    node_types (J,), or (4H, H) shared with node_types None; bias_hh or None.  `steps` = T (default:
+    the larger of Ta and Tg).  Returns (hs (B, T, J, H), s_last (B, J, H)); s_last carries no
+    gradient."""
+    if not a.is_cuda or any(v.dtype != torch.float32 for v in (a, h0, s0, gx, weight_hh)):
+        raise ValueError("graph_lstm: the HIP training path needs fp32 device tensors")
+    if a.dim() != 4 or a.shape[-1] % 4 or h0.dim() != 3:
+        raise ValueError("graph_lstm: a (B, Ta, J, 4H) and h0 (B, J, H)")
+    if gx.dim() == 2:
+        gx = gx.unsqueeze(0)
+    B, Ta, J, H4 = a.shape
+    H = H4 // 4
+    T = int(steps) if steps is not None else max(Ta, gx.shape[0])
+    if tuple(h0.shape) != (B, J, H) or tuple(s0.shape) != (B, J, H) or gx.dim() != 3 or tuple(gx.shape[1:]) != (J, J):
+        raise ValueError("graph_lstm: h0 and s0 must be (B, J, H) and gx (Tg, J, J)")
+    if (node_types is None) != (weight_hh.dim() == 2) or tuple(weight_hh.shape[-2:]) != (H4, H):
+        raise ValueError("graph_lstm: weight_hh (types, 4H, H) with node_types, or (4H, H) without")
+    if bias_hh is not None and bias_hh.numel() != weight_hh.numel() // H:
+        raise ValueError("graph_lstm: bias_hh must hold 4H values per weight type")
+    return GraphLSTMFunction.apply(a, h0, s0, gx, weight_hh, bias_hh, node_types, T,
+                                   _keeps_state(a, h0, s0, gx, weight_hh, bias_hh))
 
 
 class GxTableFunction(torch.autograd.Function):
